@@ -1,11 +1,16 @@
 """Benchmark: EEGNet-8,2 train step (forward + CE + backward + clamps + Adam) on synthetic
 22ch x 256 trials, batch 4096 per GPU, fp32, HIP kernels (BASELINE.json configs[1] / cfg4).
 
-    python bench.py [--gpus N --steps K --warmup W]            (N=1)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]        (N=1)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 Prints ONE JSON line on rank 0.  `value` = trials/s over all ranks (weak scaling: 4096 trials per
-GPU per step; N>1 = data parallel with one RCCL all-reduce per step).  `cfg4_dp` is BASELINE
+GPU per step; N>1 = data parallel with one RCCL all-reduce per step); `ms_per_step` = the wall time
+of one of the K timed steps.  A plain run does only that: set-up, the untimed steps, the K timed
+steps, the line.  `--dump-outputs DIR` then writes what the last timed step left (loss, parameters,
+BatchNorm buffers, gradients, Adam state) as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.  Everything below is measured only with
+`--full` (their keys are null in a plain run's line).  `cfg4_dp` is BASELINE
 configs[3] at its own size: global batch 65,536 split over the ranks (strong scaling).  `roofline`
 is for the kernel with the largest device time, from HIP events recorded inside the timed region,
 priced on SURVEY 8(d)'s algorithmic bytes (x reads) and the implemented FLOPs (max of the two
@@ -201,15 +206,22 @@ def pmc_step_bytes(pmc, names):
     return tot
 
 
-def timed_steps(trainer, xs, ys, steps, alg, B, barrier, prof=True, survey=5, settle=0):
+def timed_steps(trainer, xs, ys, steps, alg, B, barrier, prof=True, survey=5, settle=0, events=True):
     """Warm-up done by the caller.  An untimed 5-step survey brackets every kernel with HIP events
     (per-kernel table, dominant kernel); the timed region brackets only the dominant one.  Steps
     rotate over the distinct input buffers ``xs`` (so x comes from HBM, not the 256 MB MALL).
+    ``events=False`` (a plain run) runs the same steps on the same buffers in the same order with
+    no events at all, so the model ends in the state the instrumented run leaves.
     Returns (seconds, per-kernel survey table, dominant kernel, its (launches, ms) in the timed
     region)."""
     from eegnetreplication_amd import _lib
     table, dom, kern = {}, None, {}
     nx = len(xs)
+    if prof and not events:
+        for i in range(survey):
+            trainer.step(xs[i % nx], ys[i % nx])
+        trainer.step(xs[0], ys[0])
+        prof = False
     if prof:
         _lib.profile_enable(True)
         for i in range(survey):
@@ -299,6 +311,19 @@ def bench_train_cfg5(dev, B, steps, warmup, p=0.5):
             "step_roofline": step_roofline(fl_step, 2 * C * T * 4, sum(v[1] for v in alg.values()), tps,
                                            pmc_step_bytes(pmc, list(alg) + ["k_coltail"] * 3), B),
             "kernels": kernel_table(table, alg, B, ab)}
+
+
+def dump_outputs(out_dir, trainer):
+    """Write what the last timed step handed back and left behind, one float32 ``.npy`` per array: the
+    step's mean CE loss, the updated parameters and BatchNorm running statistics (flat, in
+    ``EEGNet.flat_views()`` order), the clamped gradients and Adam's two moments.  A few KB in all."""
+    flat, bn_flat, _ = trainer.model.flat_views()
+    n = flat.numel()
+    arrays = {"loss": trainer.loss, "params": flat, "bn_buffers": bn_flat, "grads": trainer.adam.grads,
+              "adam_exp_avg": trainer.adam.state[:n], "adam_exp_avg_sq": trainer.adam.state[n:2 * n]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def load_pmc():
@@ -725,7 +750,16 @@ def main():
     ap.add_argument("--no-cfg4", action="store_true", help="skip the cfg4 global-batch-65536 leg")
     ap.add_argument("--global-batch", type=int, default=CFG4_GLOBAL_BATCH,
                     help="cfg4 leg: global batch split over the ranks (strong scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (loss, parameters, BatchNorm "
+                         "buffers, gradients, Adam state) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: HIP-event per-kernel survey and roofline, "
+                         "cfg4 / cfg5 / inference / real-protocol fold legs, CPU baselines (each with its --no-* "
+                         "switch); a plain run times the headline steps only")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cfg4 = args.no_folds = args.no_infer = args.no_cfg5 = args.no_cpu_baseline = True
 
     from eegnetreplication_amd import EEGNet, FusedTrainer, _lib
     from eegnetreplication_amd.distributed import DataParallelTrainer, init_process_group
@@ -759,8 +793,11 @@ def main():
     alg_k, ab_k = alg, kernel_alg_bytes(C, T)
     # at least MIN_UNTIMED untimed steps in all (warm-up + survey + settle) before the K timed ones
     settle = settle_steps(args.warmup, args.survey, prof)
-    dt, table, dom, dk = timed_steps(trainer, xs, ys, args.steps, alg_k, B, barrier, prof, args.survey, settle)
+    dt, table, dom, dk = timed_steps(trainer, xs, ys, args.steps, alg_k, B, barrier, prof, args.survey, settle,
+                                     events=args.full)
     loss = float(trainer.loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)
 
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
@@ -831,6 +868,7 @@ def main():
             "warmup": args.warmup,
             "untimed_steps": args.warmup + (args.survey + 1 if prof else 0) + settle,
             "ms_per_step": round(ms_per_step, 4),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

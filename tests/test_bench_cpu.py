@@ -39,3 +39,57 @@ def test_untimed_steps_rule(warmup, survey, prof, expect):
     settle = bench.settle_steps(warmup, survey, prof)
     assert settle == expect
     assert warmup + (survey + 1 if prof else 0) + settle >= bench.MIN_UNTIMED
+
+
+class _StubModel:
+    def __init__(self, n, nb):
+        import torch
+        self.flat, self.bn = torch.arange(n, dtype=torch.float32), torch.ones(nb)
+
+    def flat_views(self):
+        return self.flat, self.bn, None
+
+
+class _StubTrainer:
+    """Records which buffer each step was given; carries the arrays dump_outputs reads."""
+
+    def __init__(self, n=6, nb=4):
+        import torch
+        from types import SimpleNamespace
+        self.model = _StubModel(n, nb)
+        self.loss = torch.tensor([1.25])
+        self.adam = SimpleNamespace(grads=torch.full((n,), 0.5), state=torch.arange(2 * n, dtype=torch.float32))
+        self.seen = []
+
+    def step(self, x, y):
+        self.seen.append((x, y))
+        return self.loss
+
+
+def test_plain_run_steps_over_the_same_buffers_as_the_instrumented_one(monkeypatch):
+    """events=False (a run without --full) records nothing, yet takes the survey's 5 + 1 steps, the
+    settle steps and the timed steps over the same buffers in the same order, so both kinds of run
+    leave the model in the same state."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    nx, survey, settle, steps = 4, 5, 7, 6
+    tr = _StubTrainer()
+    dt, table, dom, dk = bench.timed_steps(tr, list(range(nx)), list(range(10, 10 + nx)), steps, {}, 1,
+                                           lambda: None, True, survey, settle, events=False)
+    order = [i % nx for i in range(survey)] + [0] + [i % nx for i in range(settle)] + [i % nx for i in range(steps)]
+    assert tr.seen == [(i, 10 + i) for i in order]
+    assert dt > 0 and table == {} and dom is None and dk is None
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path):
+    import numpy as np
+    tr = _StubTrainer(n=6, nb=4)
+    bench.dump_outputs(str(tmp_path / "out"), tr)
+    got = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(got) == {"loss.npy", "params.npy", "bn_buffers.npy", "grads.npy", "adam_exp_avg.npy",
+                        "adam_exp_avg_sq.npy"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss.npy"].tolist() == [1.25] and got["params.npy"].tolist() == [0, 1, 2, 3, 4, 5]
+    assert got["bn_buffers.npy"].tolist() == [1] * 4 and got["grads.npy"].tolist() == [0.5] * 6
+    assert got["adam_exp_avg.npy"].tolist() == [0, 1, 2, 3, 4, 5]
+    assert got["adam_exp_avg_sq.npy"].tolist() == [6, 7, 8, 9, 10, 11]

@@ -67,6 +67,9 @@ def test_cli_within_subject_end_to_end(tmp_path, monkeypatch, fold_batch):
     dev = _dev()
     monkeypatch.chdir(tmp_path)
     monkeypatch.setenv("EEGNET_DATA_DIR", str(tmp_path / "nodata"))
+    # --synthetic writes EEGNET_SYNTHETIC=1 into this process's environment: have monkeypatch own the
+    # variable (off until the CLI turns it on) so that it is restored for the tests that follow
+    monkeypatch.setenv("EEGNET_SYNTHETIC", "0")
     cli.main(["--trainingType", "Within-Subject", "--epochs", "2", "--synthetic",
               "--fold-batch", str(fold_batch), "--out", str(tmp_path)])
     models = sorted(os.path.basename(p) for p in glob.glob(str(tmp_path / "models" / "*.pth")))
@@ -91,6 +94,7 @@ def test_cli_cross_subject_end_to_end(tmp_path, monkeypatch, fold_batch):
     dev = _dev()
     monkeypatch.chdir(tmp_path)
     monkeypatch.setenv("EEGNET_DATA_DIR", str(tmp_path / "nodata"))
+    monkeypatch.setenv("EEGNET_SYNTHETIC", "0")     # restored after the CLI's --synthetic sets it (see above)
     cli.main(["--trainingType", "Cross-Subject", "--epochs", "2", "--synthetic", "--max-units", "12",
               "--fold-batch", str(fold_batch), "--out", str(tmp_path)])
     assert os.path.exists(tmp_path / "models" / "cross_subject_best_model.pth")

@@ -69,8 +69,9 @@ def test_synthetic_sessions_shape_and_determinism():
     assert x.shape == (22, 257) and isinstance(y, int)
 
 
-def test_report_schema(tmp_path):
+def test_report_schema(tmp_path, monkeypatch):
     from eegnetreplication_amd.train import generate_cs_report, generate_ws_report
+    monkeypatch.delenv("EEGNET_SYNTHETIC", raising=False)     # the reference schema: reports on real data
     acc = [60.0, 55.5, 70.25, 40.0, 45.0, 50.0, 65.0, 66.0, 72.0]
     p = generate_ws_report(acc, float(np.mean(acc)), [None] * 9, str(tmp_path))
     r = json.load(open(p))

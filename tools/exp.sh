@@ -2,7 +2,7 @@
 # (EXP_CFG5=1: also the cfg5 training leg)
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
-X="--no-cfg5"; [ -n "$EXP_CFG5" ] && X=""
+X="--full --no-cfg5"; [ -n "$EXP_CFG5" ] && X="--full"
 for v in "$@"; do
   EEGNET_LIB=$v timeout -k 10 240 python -u bench.py --no-cpu-baseline --no-infer --no-folds $X --steps 30 --warmup 5 > gpurun_out/bench_exp.log 2>&1 || { tail -20 gpurun_out/bench_exp.log; exit 1; }
   python -c "

@@ -15,6 +15,7 @@ if [ -z "$NOTESTS" ]; then
   tail -1 gpurun_out/${TAG}_smoke.log
 fi
 if [ -z "$NOBENCH" ]; then
+  BENCH_ARGS="--full ${BENCH_ARGS}"      # every leg of the bench line, not the headline alone
   timeout -k 10 600 python -u bench.py ${BENCH_ARGS} > gpurun_out/${TAG}_bench.log 2>&1 || { echo BENCH_FAILED; tail -30 gpurun_out/${TAG}_bench.log; exit 1; }
   tail -1 gpurun_out/${TAG}_bench.log | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); f=d.get('real_protocol_folds') or {}; c=d.get('cfg5_train') or {}; i=d.get('cfg5_infer_bf16') or {}

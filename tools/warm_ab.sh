@@ -4,7 +4,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
-Q="--no-cpu-baseline --no-infer --no-folds --no-cfg5 --no-cfg4"
+Q="--full --no-cpu-baseline --no-infer --no-folds --no-cfg5 --no-cfg4"
 for i in 1 2 3; do
   for v in "--steps 20 --warmup 5 --survey 5" "--steps 20 --warmup 5 --survey 20" "--steps 20 --warmup 60 --survey 5" "--steps 100 --warmup 5 --survey 5"; do
     timeout -k 10 120 python -u bench.py $v $Q > gpurun_out/warm.log 2>&1 || { echo FAIL; tail -5 gpurun_out/warm.log; exit 1; }
