@@ -49,6 +49,8 @@ _SIGS = {
                                        ctypes.c_int]),
     "eegnet_clamp_grads": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp]),
     "eegnet_forward_eval": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp]),
+    "eegnet_input_grad_eval": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int, _vp, _vp,
+                                              _vp, _vp, _vp]),
     "eegnet_forward_eval_bf16": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp]),
     "eegnet_adam_step": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
@@ -137,7 +139,7 @@ def workspace_bytes(d: Dims) -> int:
 
 KERNEL_IDS = ("k_pass_a", "k_pass_b", "k_pass_c", "k_pass_d", "k_pass_e", "k_adam", "k_infer",
               "memset_tickets", "k_infer_bf16", "k_wpass_a", "k_wpass_b", "k_wpass_b2", "k_wpass_c",
-              "k_wpass_d", "k_wpass_e", "k_winfer", "k_coltail", "k_xstats")
+              "k_wpass_d", "k_wpass_e", "k_winfer", "k_coltail", "k_xstats", "k_infer_dx")
 
 
 def profile_enable(on: bool = True, kernels=None):

@@ -170,6 +170,9 @@ static int make_geo(const eegnet_dims* d, Geo* g, bool launch = true) {
     g->ldsE = std::max((2 * g->F2 + g->C) * g->RS + rup(g->F2 * g->T1, 4) + 8 * g->F2,
                        NWB * 256 * (1 + (15 + g->K1 - 1) / 16 + 1));   // after the loop: dws, Cq tiles
     g->ldsI = rows1 + g->F2 * g->RS + 2 * g->F2 * g->RS2 + nf4;
+    // k_infer_dx: x rows (then the dx staging rows), s rows (then al dz2), the ELU'(z2) plane (then ds),
+    // d2 / q rows (then dr / dq), h, the trial's logits; checked by eegnet_input_grad_eval alone
+    g->ldsX = rows1 + 2 * g->F2 * g->RS + 2 * g->F2 * g->RS2 + nf4 + 4;
     // the reduction tail and finalize reuse each pass kernel's LDS (doubles = 2 floats)
     auto tail = [](int ncols, int fin) { return 2 * (tail_s_doubles(ncols) + std::max(tail_scratch_doubles(ncols), fin)); };
     g->ldsA = std::max(g->ldsA, tail(g->nA, fin1_scratch_doubles(g->K1, g->F1, g->F2, g->C)));
@@ -298,11 +301,12 @@ static void set_key(Geo* g, uint64_t seed, uint64_t offset) {
 
 // ---- optional per-kernel device timing (bench / roofline), off by default ----
 enum KernelId { KID_A = 0, KID_B, KID_C, KID_D, KID_E, KID_ADAM, KID_INFER, KID_MEMSET, KID_INFER_BF16,
-                KID_WA, KID_WB, KID_WB2, KID_WC, KID_WD, KID_WE, KID_WINFER, KID_CTAIL, KID_XSTATS, KID_COUNT };
+                KID_WA, KID_WB, KID_WB2, KID_WC, KID_WD, KID_WE, KID_WINFER, KID_CTAIL, KID_XSTATS, KID_INFER_DX,
+                KID_COUNT };
 static const char* kKernelNames[KID_COUNT] = {"k_pass_a", "k_pass_b", "k_pass_c", "k_pass_d", "k_pass_e",
                                               "k_adam", "k_infer", "memset_tickets", "k_infer_bf16",
                                               "k_wpass_a", "k_wpass_b", "k_wpass_b2", "k_wpass_c", "k_wpass_d",
-                                              "k_wpass_e", "k_winfer", "k_coltail", "k_xstats"};
+                                              "k_wpass_e", "k_winfer", "k_coltail", "k_xstats", "k_infer_dx"};
 #ifndef EEGNET_PROF_EVENT_FLAGS
 #define EEGNET_PROF_EVENT_FLAGS hipEventDisableSystemFence
 #endif
@@ -354,6 +358,7 @@ static void set_attrs_shape() {
                           (const void*)k_pass_dr<K1, CC, TT, FF, true, false>})
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_infer<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)k_infer_dx<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 template <int K1>
@@ -818,6 +823,35 @@ int eegnet_forward_eval(const eegnet_dims* dims, const float* params, const floa
                                                    g, params, bn_buffers, x, logits)
     if (g.K1 == 32) EEG_DISPATCH(32, g, LAUNCH_I); else EEG_DISPATCH(64, g, LAUNCH_I);
     LAUNCH_CHECK("k_infer");
+    return 0;
+}
+
+int eegnet_input_grad_eval(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                           const float* x, int seed_kind, const float* dlogits, const int64_t* targets,
+                           float* dx, float* logits, void* stream) {
+    Geo g;
+    if (int r = make_geo(dims, &g, false)) return r;
+    if (g.wide) return fail(EEGNET_EINVAL, "input gradients: F1*D = %d > 16 is not supported", g.F2);
+    if (int r = make_geo(dims, &g)) return r;
+    if (g.XP != g.T) return fail(EEGNET_EINVAL, "input gradients take x as [B][C][T] (x_pitch 0 or T)");
+    if (seed_kind < EEGNET_SEED_DLOGITS || seed_kind > EEGNET_SEED_CE)
+        return fail(EEGNET_EINVAL, "seed_kind must be 0 (dlogits), 1 (logit) or 2 (cross-entropy) (got %d)", seed_kind);
+    if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
+    if (int r = check_ptrs(x, "x", dx, "dx")) return r;
+    if (seed_kind == EEGNET_SEED_DLOGITS && !dlogits) return fail(EEGNET_EINVAL, "EEGNET_SEED_DLOGITS needs dlogits");
+    if (seed_kind == EEGNET_SEED_CE && !targets) return fail(EEGNET_EINVAL, "EEGNET_SEED_CE needs targets");
+    if (g.ldsX * 4 > LDS_MAX)
+        return fail(EEGNET_EINVAL, "input gradients: dims need %d B of LDS (> %d)", g.ldsX * 4, LDS_MAX);
+    if ((g.T & 3) == 0 && ((uintptr_t)x & 15)) return fail(EEGNET_EINVAL, "input gradients: x must be 16-byte aligned");
+    // dx rows go out in 16-byte stores only when every row of it starts 16-byte aligned
+    const int vec = (g.T & 3) == 0 && ((uintptr_t)dx & 15) == 0;
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    PROF(KID_INFER_DX);
+#define LAUNCH_X(K, CC, TT, FF) hipLaunchKernelGGL((k_infer_dx<K, CC, TT, FF>), dim3(g.grid), dim3(NTH), g.ldsX * 4, s, \
+                                                   g, params, bn_buffers, x, seed_kind, dlogits, targets, dx, logits, vec)
+    if (g.K1 == 32) EEG_DISPATCH(32, g, LAUNCH_X); else EEG_DISPATCH(64, g, LAUNCH_X);
+    LAUNCH_CHECK("k_infer_dx");
     return 0;
 }
 

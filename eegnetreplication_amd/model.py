@@ -201,6 +201,13 @@ class EEGNet(nn.Module):
 
     # -- forward -------------------------------------------------------------------------------
     def forward(self, x):
+        """Logits [B, 4] of x [B, C, T] on the HIP kernels.
+
+        In eval mode an input with ``requires_grad`` (grad enabled, F1*D <= 16) gets a differentiable
+        forward: ``backward()`` fills ``x.grad`` with one fused eval-mode input-gradient launch.  That
+        node is differentiable with respect to x ONLY -- the parameters are not its inputs, so every
+        ``param.grad`` stays ``None``; parameter gradients come from the train-mode forward.  Train
+        mode does not provide input gradients (they need the batch-global BatchNorm backward)."""
         require_device(x, "EEGNet input")
         if x.dtype == torch.bfloat16 and not self.training:
             # bf16 batched inference (SURVEY 8(f) row 4): bf16 MFMA operands, fp32 accumulation
@@ -214,7 +221,11 @@ class EEGNet(nn.Module):
         if x.dim() != 3 or x.shape[1] != self.C or x.shape[2] != self.T:
             raise RuntimeError(f"expected input [B,{self.C},{self.T}], got {list(x.shape)}")
         if x.requires_grad:
-            raise NotImplementedError("gradients with respect to the EEG input are not provided")
+            if self.training or not torch.is_grad_enabled() or self.F1 * self.D > 16:
+                raise NotImplementedError("gradients with respect to the EEG input are not provided")
+            flat = self.flat_parameters()
+            require_device(flat, "EEGNet parameters")
+            return _EvalInputGradFn.apply(x, self, self.shape)
         x = x.contiguous()
         flat = self.flat_parameters()
         require_device(flat, "EEGNet parameters")
@@ -271,6 +282,78 @@ class _EvalFn(torch.autograd.Function):
         raise NotImplementedError(
             "backward through an eval-mode EEGNet forward is not provided; call model.train() "
             "for a differentiable forward")
+
+
+class _EvalInputGradFn(torch.autograd.Function):
+    """Eval-mode forward that is differentiable with respect to x only: forward = the fused inference
+    kernel, backward(dlogits) = one eegnet_input_grad_eval launch (EEGNET_SEED_DLOGITS).  The
+    parameters are not inputs of the node, so they receive no gradient.  The backward runs on the
+    parameters and running statistics as they are at that moment."""
+
+    @staticmethod
+    def forward(ctx, x, mod, shape):
+        xc = x.detach().contiguous()
+        ctx.mod, ctx.shape = mod, shape
+        ctx.save_for_backward(xc)
+        return ops.forward_eval(shape, mod.flat_parameters(), mod.flat_bn_buffers(), xc)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        (x,) = ctx.saved_tensors
+        mod = ctx.mod
+        dx, _ = ops.input_grad_eval(ctx.shape, mod.flat_parameters(), mod.flat_bn_buffers(), x,
+                                    kind="dlogits", dlogits=dlogits)
+        return dx, None, None
+
+
+def saliency(model, x, targets=None, kind="logit"):
+    """Input gradient of an EEGNet decision: ``(dx, logits)`` for x [B, C, T], in one fused launch and
+    with no autograd graph.  ``kind="logit"``: dx[b] = d logits[b, targets[b]] / dx[b], the predicted
+    class when ``targets`` is None; ``kind="ce"``: the gradient of the trial's cross-entropy against
+    ``targets``.  Always eval semantics (running statistics, no dropout), whatever ``model.training``
+    is, and that mode is left untouched.  F1*D > 16 models raise NotImplementedError."""
+    if kind not in ("logit", "ce"):
+        raise ValueError(f"kind must be 'logit' or 'ce' (got {kind!r})")
+    if kind == "ce" and targets is None:
+        raise ValueError("kind='ce' needs targets")
+    require_device(x, "EEGNet input")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"saliency expects float32 input (got {x.dtype})")
+    if x.dim() != 3 or x.shape[1] != model.C or x.shape[2] != model.T:
+        raise RuntimeError(f"expected input [B,{model.C},{model.T}], got {list(x.shape)}")
+    flat = model.flat_parameters()
+    require_device(flat, "EEGNet parameters")
+    with torch.no_grad():
+        try:
+            return ops.input_grad_eval(model.shape, flat, model.flat_bn_buffers(), x.detach(), kind=kind,
+                                       targets=targets)
+        except RuntimeError as e:
+            if "is not supported" in str(e):
+                raise NotImplementedError(str(e)) from None
+            raise
+
+
+def relevance_maps(model, loader, method="gradxinput"):
+    """Per-class input-relevance maps [4, C, T]: the mean over the trials of each TRUE class of
+    |dx * x| (``method="gradxinput"``) or |dx| (``"grad"``), dx being the saliency of the true-class
+    logit, over a loader of (signals, labels).  Accumulated on the device in float64 with one host
+    sync at the end; a class without trials gets a zero map."""
+    if method not in ("gradxinput", "grad"):
+        raise ValueError(f"method must be 'gradxinput' or 'grad' (got {method!r})")
+    device = _device()
+    model = model.to(device)
+    acc = torch.zeros((ops.NCLS, model.C, model.T), dtype=torch.float64, device=device)
+    cnt = torch.zeros(ops.NCLS, dtype=torch.float64, device=device)
+    for signals, labels in loader:
+        signals = signals.float().to(device, non_blocking=True)
+        labels = labels.to(device, non_blocking=True).long()
+        dx, _ = saliency(model, signals, targets=labels, kind="logit")
+        rel = (dx * signals if method == "gradxinput" else dx).abs().double()
+        acc.index_add_(0, labels, rel)
+        cnt += torch.bincount(labels, minlength=ops.NCLS)[:ops.NCLS]
+    out = (acc / cnt.clamp(min=1.0).view(-1, 1, 1)).float()
+    return out.cpu()
 
 
 # ----------------------------------------------------------------------------------------------

@@ -154,6 +154,44 @@ def forward_eval(shape: Shape, flat_params, bn_flat, x) -> torch.Tensor:
     return logits
 
 
+SEED_DLOGITS, SEED_LOGIT, SEED_CE = 0, 1, 2     # include/eegnet_abi.h EEGNET_SEED_*
+_SEED_KINDS = {"dlogits": SEED_DLOGITS, "logit": SEED_LOGIT, "ce": SEED_CE}
+
+
+def input_grad_eval(shape: Shape, flat_params, bn_flat, x, *, kind, dlogits=None, targets=None, out=None):
+    """Eval-mode input gradient (eegnet_input_grad_eval, one fused launch): ``(dx, logits)`` with
+    dx[b] = d(g[b] . logits[b]) / dx[b].  ``kind``: "dlogits" (g = ``dlogits`` [B, 4]), "logit"
+    (g = onehot(``targets``), the trial's own argmax when ``targets`` is None) or "ce"
+    (g = softmax(logits) - onehot(``targets``)).  ``out``: a contiguous float32 [B, C, T] tensor to
+    receive dx (any 4-byte alignment) instead of a new one."""
+    if kind not in _SEED_KINDS:
+        raise ValueError(f"kind must be one of {sorted(_SEED_KINDS)} (got {kind!r})")
+    require_device(x, "x")
+    x = x.contiguous()                # the eval kernels read [B][C][T] rows (no pitch)
+    B = x.shape[0]
+    if dlogits is not None:
+        dlogits = dlogits.to(device=x.device, dtype=torch.float32).contiguous()
+        if tuple(dlogits.shape) != (B, NCLS):
+            raise ValueError(f"dlogits must be [{B}, {NCLS}] (got {list(dlogits.shape)})")
+    if targets is not None:
+        targets = targets.to(device=x.device, dtype=torch.int64).contiguous()
+        if tuple(targets.shape) != (B,):
+            raise ValueError(f"targets must be [{B}] (got {list(targets.shape)})")
+    if out is None:
+        out = torch.empty_like(x)
+    elif (out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != x.device):
+        raise ValueError(f"out must be a contiguous float32 {list(x.shape)} tensor on {x.device}")
+    logits = torch.empty((B, NCLS), dtype=torch.float32, device=x.device)
+    if B == 0:
+        return out, logits
+    d = shape.dims(B)
+    _lib.check(_lib.load().eegnet_input_grad_eval(
+        ctypes.byref(d), _ptr(flat_params), _ptr(bn_flat), _ptr(x), ctypes.c_int(_SEED_KINDS[kind]),
+        _ptr(dlogits), _ptr(targets), _ptr(out), _ptr(logits), _stream()), "eegnet_input_grad_eval")
+    return out, logits
+
+
 def forward_eval_bf16(shape: Shape, flat_params, bn_flat, x) -> torch.Tensor:
     """Eval-mode forward on bf16 input (bf16 MFMA operands, fp32 accumulation, fp32 logits)."""
     if x.dtype != torch.bfloat16:

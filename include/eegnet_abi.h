@@ -6,6 +6,7 @@
  *   loss.backward() + hooks   src/eegnet_repl/model.py:44,84,147 -> eegnet_backward
  *   optimizer.step() (Adam)   src/eegnet_repl/train.py:94-101, model.py:148 -> eegnet_adam_step
  *   one hot-loop iteration    src/eegnet_repl/model.py:136-148 -> eegnet_train_step
+ *   saliency / x.grad in .eval() (plain autograd on the nn.Module) -> eegnet_input_grad_eval
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer (hipMalloc / torch CUDA tensor) unless noted.  The library never
@@ -107,6 +108,26 @@ int eegnet_clamp_grads(const eegnet_dims* dims, float* grads, void* stream);
 int eegnet_forward_eval(const eegnet_dims* dims, const float* params, const float* bn_buffers,
                         const float* x, float* logits, void* stream);
 
+/* Seed of eegnet_input_grad_eval: the per-trial gradient g[4] with respect to the logits. */
+enum { EEGNET_SEED_DLOGITS = 0,  /* g = dlogits[b]                                   */
+       EEGNET_SEED_LOGIT   = 1,  /* g = onehot(targets[b]); targets NULL: the trial's */
+                                 /*     own argmax (lowest index on a tie)            */
+       EEGNET_SEED_CE      = 2 };/* g = softmax(logits[b]) - onehot(targets[b])       */
+                                 /*     (per-trial CE, reduction "sum")               */
+
+/* Eval-mode input gradient (saliency): dx[b] = d(g[b] . logits[b]) / dx[b] with running statistics and
+ * no dropout, so every trial is independent.  One fused kernel runs the forward of eegnet_forward_eval
+ * and its transposed chain per trial without leaving the CU; the logits it computes on the way are
+ * written to `logits` [B,4] when non-NULL.  dlogits [B,4] is read for EEGNET_SEED_DLOGITS only; targets
+ * int64 [B] is required for EEGNET_SEED_CE and optional for EEGNET_SEED_LOGIT.  dx is [B,C,T] fp32
+ * (any 4-byte alignment; no byte outside it is written); x is 16-byte aligned when T % 4 == 0, and
+ * x_pitch must be 0 or T.  F1*D <= 16 only
+ * (wide dims return EEGNET_EINVAL); gradients of train-mode BatchNorm are not provided.  The
+ * validation needs no GPU. */
+int eegnet_input_grad_eval(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                           const float* x, int seed_kind, const float* dlogits,
+                           const int64_t* targets, float* dx, float* logits, void* stream);
+
 /* bf16 batched eval-mode forward (BASELINE cfg5, EEGNet-16,4 at 64ch x 512):
  * the same function as eegnet_forward_eval (model.py:91-99 in .eval(), called at model.py:161/220,
  * ui.py:35) on bf16 input x [B,C,T] (16-byte aligned when T % 8 == 0), bf16 MFMA operands and fp32
@@ -202,7 +223,7 @@ int eegnet_x_stats(const eegnet_dims* dims, int64_t n, const float* x, float* ou
 /* Optional per-kernel device timing for benchmarks: `on` is a bitmask of kernel ids (bit i = the
  * i-th name eegnet_profile_collect reports: k_pass_a, k_pass_b, k_pass_c, k_pass_d, k_pass_e,
  * k_adam, k_infer, memset_tickets, k_infer_bf16, k_wpass_a, k_wpass_b, k_wpass_b2, k_wpass_c,
- * k_wpass_d, k_wpass_e, k_winfer, k_coltail, k_xstats; -1 = all, 0 = off; the k_w* kernels are the F2 > 16 path).  Every selected kernel this
+ * k_wpass_d, k_wpass_e, k_winfer, k_coltail, k_xstats, k_infer_dx; -1 = all, 0 = off; the k_w* kernels are the F2 > 16 path).  Every selected kernel this
  * thread launches through the calls above is bracketed by hipEvents.  eegnet_profile_collect
  * synchronises them and reports, per kernel name (32-byte slots in `names`), launch count and
  * summed device ms; it returns the number of kernels in *n_out.  Not for use under hipGraph
