@@ -51,6 +51,13 @@ _SIGS = {
     "eegnet_forward_eval": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp]),
     "eegnet_input_grad_eval": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int, _vp, _vp,
                                               _vp, _vp, _vp]),
+    "eegnet_frozen_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.POINTER(ctypes.c_size_t)]),
+    "eegnet_forward_frozen": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
+                                             ctypes.c_uint64, _vp, _vp]),
+    "eegnet_frozen_step": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_float,
+                                          ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp,
+                                          ctypes.c_int]),
     "eegnet_forward_eval_bf16": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp]),
     "eegnet_adam_step": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),

@@ -1,0 +1,576 @@
+// eegnet_frozen.hip -- frozen-BatchNorm fine-tuning: the fused forward + loss + backward + parameter
+// gradient kernel behind eegnet_frozen_step / eegnet_forward_frozen, and the reduction of its
+// per-workgroup partial rows.  Included by eegnet_kernels.hip (one translation unit).
+//
+// With the BatchNorm layers frozen (running statistics used and left untouched, dropout still on)
+// every trial is independent: none of the five batch-global reductions that split the train step into
+// passes A..E exist, and the whole chain of a trial stays on one CU.  With
+// a1 = g1/sd1, c1 = b1 - a1 rm1, W_o = sum_c ws[o,c], s2 = g2/sd2, s3 = g3/sd3:
+//     forward   s = ws x;  v = FIR_w1(s);  u = a1 v + c1 W_o;  z2 = s2 (u - rm2) + b2
+//               d2 = pool4(ELU(z2)) m2/(1-p);  q = FIR_w2(d2);  r = W3 q
+//               z3 = s3 (r - rm3) + b3;  h = pool8(ELU(z3)) m3/(1-p);  logits = Wfc h + bfc
+//     seed      g = dlogits[b]  or  (softmax(logits[b]) - onehot(label[b])) / B   (loss += CE/B)
+//     backward  dWfc += g (x) h;  dbfc += g;  dh = Wfc^T g;  dz3 = dh/8 m3/(1-p) ELU'(z3)
+//               dg3 += sum dz3 (r - rm3)/sd3;  db3 += sum dz3;  dr = s3 dz3
+//               dW3 += dr q^T;  dq = W3^T dr;  dw2[o,k] += sum_t dq[o,t] d2[o,t+k-7];  dd2 = FIR^T_w2(dq)
+//               dz2 = dd2/4 m2/(1-p) ELU'(z2);  dg2 += sum dz2 (u - rm2)/sd2;  db2 += sum dz2;  du = s2 dz2
+//               dg1[g] += sum_{o in g} sum_t du (v - rm1 W_o)/sd1;  db1[g] += sum_{o in g} W_o sum_t du
+//               dw1[g,k] += a1 sum_{o in g} sum_t du[o,t] s[o,t+k-P]
+//               dws[o,c] += a1 sum_t ds'[o,t] x[c,t] + c1 sum_t du[o,t],   ds' = FIR^T_w1(du)
+// k_frozen has k_infer_dx's shape: 1024 threads, wave o owns row o of every [F2, T] plane, one workgroup
+// per trial in flight, trials strided over the grid, the next trial's x prefetched into registers.  LDS
+// (floats, make_geo's ldsX -- the same plan as k_infer_dx):
+//     Xs [C][RS]     x rows, kept until the dws product
+//     Ss [F2][RS]    s rows; after the dw1 correlation, ds'
+//     Vs [F2][RS]    v rows; then du
+//     D2s [F2][RS2]  d2 rows (left pad LP2)
+//     Qs [F2][RS2]   q rows (left pad LP2); then dr (all rows are read by every wave), then dq
+//     Hs [NF], Lg [4]
+// The pads of every padded row are zeroed once and never written, so nothing of a trial (a NaN
+// included) reaches the next one.
+//
+// Gradient sums.  Everything a lane can keep cheaply stays in registers across the workgroup's trials
+// (the per-row BatchNorm sums, the classifier products, the dws MFMA accumulators); the three lag /
+// channel correlations (dw1, dw2, dW3) are reduced over the wave once per trial and added, by a fixed
+// lane in trial order, to the workgroup's own partial row in global memory.  The partial row holds raw
+// sums (FzCols); k_frozen_reduce sums the rows over the workgroups in workgroup order in fp64, applies
+// the trial-invariant factors (a1, c1, W_o, 1/sd1), sums the rows of a temporal group, clamps and writes
+// `grads` and `loss`.  No atomics anywhere: the bits depend on the launch grid, not on scheduling.
+
+namespace eeg {
+
+// columns of one workgroup's partial row (floats)
+struct FzCols {
+    int w1;     // [F2][K1]  sum_t du[o,t] s[o,t+k-P]
+    int dv;     // [F2]      sum_t du v
+    int su;     // [F2]      sum_t du
+    int ws;     // [F2][C]   sum_t ds'[o,t] x[c,t]
+    int g2, b2; // [F2]
+    int w2;     // [F2][16]
+    int W3;     // [F2][F2]
+    int g3, b3; // [F2]
+    int Wfc;    // [4][NF]
+    int bfc;    // [4]
+    int loss;   // [1]
+    int n;
+};
+__host__ __device__ inline FzCols fz_cols(const Geo& g) {
+    FzCols c;
+    int o = 0;
+    c.w1 = o; o += g.F2 * g.K1;
+    c.dv = o; o += g.F2;
+    c.su = o; o += g.F2;
+    c.ws = o; o += g.F2 * g.C;
+    c.g2 = o; o += g.F2;
+    c.b2 = o; o += g.F2;
+    c.w2 = o; o += g.F2 * K2;
+    c.W3 = o; o += g.F2 * g.F2;
+    c.g3 = o; o += g.F2;
+    c.b3 = o; o += g.F2;
+    c.Wfc = o; o += NCLS * g.NF;
+    c.bfc = o; o += NCLS;
+    c.loss = o; o += 1;
+    c.n = o;
+    return c;
+}
+
+// this workgroup's running sum in its partial row: a plain store for its first trial (the row needs no
+// zeroing), a read-modify-write by the same lane afterwards
+__device__ __forceinline__ void fz_add(float* p, float v, bool first) { *p = first ? v : *p + v; }
+
+template <int K1, int CC, int TT, int FF, bool BWD>
+__global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__ prm,
+                                                const float* __restrict__ bn, const float* __restrict__ x,
+                                                const float* __restrict__ dlog, const int64_t* __restrict__ lab,
+                                                const uint8_t* __restrict__ m2, const uint8_t* __restrict__ m3,
+                                                float* __restrict__ logits, float* part) {
+    using G_ = KG<K1>;
+    EEG_DIMS(g);
+    constexpr int NCTM = CC ? (CC + 15) / 16 : 4;      // 16-channel tiles of the dws product (C <= 64)
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* const Xs = sm;
+    float* const Ss = Xs + C * RS;
+    float* const Vs = Ss + F2 * RS;
+    float* const D2s = Vs + F2 * RS;
+    float* const Qs = D2s + F2 * RS2;
+    float* const Hs = Qs + F2 * RS2;
+    float* const Lg = Hs + ((NF + 3) & ~3);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lk = lane >> 4;
+    const float* rm1 = bn;                 const float* rv1 = bn + g.F1;
+    const float* rm2 = bn + 2 * g.F1;      const float* rv2 = rm2 + F2;
+    const float* rm3 = rm2 + 2 * F2;       const float* rv3 = rm3 + F2;
+
+    for (int i = tid; i < (C + 2 * F2) * RS + 2 * F2 * RS2; i += NTH) sm[i] = 0.f;
+    float aw[KS];
+    load_ws_frag<KS>(prm + g.o_ws, C, F2, aw, lane);
+    const int o = wave;
+    const bool row_on = o < F2;
+    const int oo = row_on ? o : 0, gg = oo / g.D;
+    float tap[K1];
+#pragma unroll
+    for (int k = 0; k < K1; ++k) tap[k] = prm[g.o_w1 + gg * K1 + k];
+    const float tapl = lane < K1 ? prm[g.o_w1 + gg * K1 + lane] : 0.f;     // tap `lane` (the ds' tail samples)
+    float w2[K2], w3[F2MAX];
+#pragma unroll
+    for (int k = 0; k < K2; ++k) w2[k] = prm[g.o_w2 + oo * K2 + k];
+#pragma unroll
+    for (int i = 0; i < F2MAX; ++i) w3[i] = i < F2 ? prm[g.o_W3 + oo * F2 + i] : 0.f;
+    // frozen BN1 and BN2 folded: z2 = al v + be, (u - rm2)/sd2 = ax v + bx; BN3: z3 = s3 r + b3
+    float al, be, ax, bx, s2, s3, b3, i3, m3o;
+    {
+        const float a1 = prm[g.o_g1 + gg] / sqrtf(rv1[gg] + g.eps);
+        const float c1 = prm[g.o_b1 + gg] - a1 * rm1[gg];
+        float W = 0.f;
+        for (int c = 0; c < C; ++c) W += prm[g.o_ws + oo * C + c];
+        const float i2 = 1.f / sqrtf(rv2[oo] + g.eps);
+        s2 = prm[g.o_g2 + oo] * i2;
+        al = a1 * s2;
+        be = (c1 * W - rm2[oo]) * s2 + prm[g.o_b2 + oo];
+        ax = a1 * i2;
+        bx = (c1 * W - rm2[oo]) * i2;
+        i3 = 1.f / sqrtf(rv3[oo] + g.eps);
+        s3 = prm[g.o_g3 + oo] * i3;
+        m3o = rm3[oo];
+        b3 = prm[g.o_b3 + oo] - m3o * s3;
+    }
+    const unsigned key0 = g.drop ? drop_key(g, 0) : 0u, key1 = g.drop ? drop_key(g, 1) : 0u;
+    const float invB = 1.f / (float)g.B;
+    // sums kept in registers across this workgroup's trials
+    float aG3 = 0.f, aB3 = 0.f, aG2 = 0.f, aB2 = 0.f, aDV = 0.f, aSU = 0.f, aLoss = 0.f;
+    float aFc[NCLS] = {0.f, 0.f, 0.f, 0.f}, aBfc[NCLS] = {0.f, 0.f, 0.f, 0.f};
+    floatx4 aWs[NCTM];
+#pragma unroll
+    for (int ct = 0; ct < NCTM; ++ct) aWs[ct] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    const FzCols fc = fz_cols(g);
+    float* const prow = BWD ? part + (size_t)blockIdx.x * fc.n : nullptr;
+
+    const size_t nx = (size_t)C * T;
+    float pf[PF];
+    if ((int)blockIdx.x < g.B) x_prefetch<PF>(x + (size_t)blockIdx.x * nx, C, T, pf, tid);
+    __syncthreads();
+    x_store<PF>(pf, C, T, RS, LP, Xs, tid);
+    __syncthreads();
+    drain_prologue_loads();
+
+    for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
+        const int bnx = b + gridDim.x;
+        const bool first = b == (int)blockIdx.x;
+        if (bnx < g.B) x_prefetch<PF>(x + (size_t)bnx * nx, C, T, pf, tid);
+        // ---------------- forward ----------------
+        spatial_mfma<KS>(Xs, aw, Ss, C, F2, NT16, RS, LP, wave, lane);
+        __syncthreads();                                   // s rows complete
+        if (row_on) {
+            const float* row = Ss + o * RS;
+            float* vrow = Vs + o * RS + LP;
+            float* drow = D2s + o * RS2 + LP2;
+            const unsigned i2 = ((unsigned)b * (unsigned)F2 + (unsigned)o) * (unsigned)T1;
+            for (int q = lane; q < T1; q += 64) {
+                float w[4 * G_::NW];
+                lds_window<G_::NW>(row + 4 * q, w);
+                float v[4];
+                fir4<K1, G_::OFF>(w, tap, v);
+                float pe = 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pe += elu_f(fmaf(al, v[i], be));
+                drow[q] = pe * 0.25f * keep_mul(g, m2, key0, i2 + (unsigned)q);
+                lds_st4(vrow + 4 * q, (floatx4){v[0], v[1], v[2], v[3]});
+            }
+            wave_lds_fence();
+            // block_2 depthwise: q[t] = sum_k w2[k] d2[t + k - 7]
+            const float* dr = D2s + o * RS2 + 1;
+            float* qrow = Qs + o * RS2 + LP2;
+#pragma unroll
+            for (int m = 0; m < MAXT1Q; ++m) {
+                const int t = lane + 64 * m;
+                if (t < T1) {
+                    float a = 0.f;
+#pragma unroll
+                    for (int k = 0; k < K2; ++k) a = fmaf(w2[k], dr[t + k], a);
+                    qrow[t] = a;
+                }
+            }
+        }
+        __syncthreads();                                   // q rows complete
+        float r[MAXT1Q];
+#pragma unroll
+        for (int m = 0; m < MAXT1Q; ++m) {
+            const int t = lane + 64 * m;
+            float a = 0.f;
+            if (row_on && t < T1) {
+#pragma unroll
+                for (int i = 0; i < F2MAX; ++i)
+                    if (i < F2) a = fmaf(w3[i], Qs[i * RS2 + LP2 + t], a);
+            }
+            r[m] = a;
+        }
+        const unsigned i3b = ((unsigned)b * (unsigned)F2 + (unsigned)oo) * (unsigned)T2;
+#pragma unroll
+        for (int m = 0; m < MAXT1Q; ++m) {
+            const int t = lane + 64 * m;
+            const bool on = row_on && t < 8 * T2;
+            float e = on ? elu_f(fmaf(s3, r[m], b3)) : 0.f;
+            e += dpp<0xB1>(e);                 // 8-lane sums by DPP (xor 1, xor 2, half-row mirror)
+            e += dpp<0x4E>(e);
+            e += dpp<0x141>(e);
+            if (on && (t & 7) == 0)
+                Hs[o * T2 + (t >> 3)] = e * 0.125f * keep_mul(g, m3, key1, i3b + (unsigned)(t >> 3));
+        }
+        __syncthreads();                                   // h complete
+        if (wave < NCLS) {
+            const int n = wave;
+            float a = 0.f;
+            for (int i = lane; i < NF; i += 64) a = fmaf(prm[g.o_Wfc + n * NF + i], Hs[i], a);
+            a = wave_sum(a);
+            if (lane == 0) {
+                const float l = a + prm[g.o_bfc + n];
+                Lg[n] = l;
+                if (logits) logits[(size_t)b * NCLS + n] = l;
+            }
+        }
+        __syncthreads();                                   // logits of this trial in Lg
+        if constexpr (BWD) {
+            // ---------------- seed g = dL/dlogits of this trial ----------------
+            float gs[NCLS];
+            if (dlog) {
+#pragma unroll
+                for (int n = 0; n < NCLS; ++n) gs[n] = dlog[(size_t)b * NCLS + n];
+            } else {                                       // mean cross-entropy: (softmax - onehot) / B
+                float l[NCLS];
+#pragma unroll
+                for (int n = 0; n < NCLS; ++n) l[n] = Lg[n];
+                const int cls = (int)lab[b];
+                const float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
+                float ex[NCLS], sum = 0.f, lc = 0.f;
+#pragma unroll
+                for (int n = 0; n < NCLS; ++n) { ex[n] = expf(l[n] - mx); sum += ex[n]; lc = n == cls ? l[n] : lc; }
+#pragma unroll
+                for (int n = 0; n < NCLS; ++n) gs[n] = (ex[n] / sum - (n == cls ? 1.f : 0.f)) * invB;
+                aLoss += (logf(sum) + mx - lc) * invB;
+            }
+            // ---------------- backward ----------------
+#pragma unroll
+            for (int n = 0; n < NCLS; ++n) aBfc[n] += gs[n];
+            if (tid < NF) {
+                const float h = Hs[tid];
+#pragma unroll
+                for (int n = 0; n < NCLS; ++n) aFc[n] = fmaf(gs[n], h, aFc[n]);
+            }
+            float drv[MAXT1Q];
+            if (row_on) {
+                // dz3 = dh/8 m3/(1-p) ELU'(z3), dh = Wfc^T g; BN3 sums; dr = s3 dz3 (registers)
+                const float* wfc = prm + g.o_Wfc + o * T2;
+#pragma unroll
+                for (int m = 0; m < MAXT1Q; ++m) {
+                    const int t = lane + 64 * m;
+                    float v = 0.f;
+                    if (t < 8 * T2) {
+                        float dh = 0.f;
+#pragma unroll
+                        for (int n = 0; n < NCLS; ++n) dh = fmaf(wfc[n * NF + (t >> 3)], gs[n], dh);
+                        const float dz3 = 0.125f * dh * keep_mul(g, m3, key1, i3b + (unsigned)(t >> 3)) *
+                                          elu_d(fmaf(s3, r[m], b3));
+                        aG3 = fmaf(dz3, (r[m] - m3o) * i3, aG3);
+                        aB3 += dz3;
+                        v = s3 * dz3;
+                    }
+                    drv[m] = v;
+                }
+                // dW3[o,i] += sum_t dr[o,t] q[i,t]
+                float cw[F2MAX];
+#pragma unroll
+                for (int i = 0; i < F2MAX; ++i) cw[i] = 0.f;
+#pragma unroll
+                for (int m = 0; m < MAXT1Q; ++m) {
+                    const int t = lane + 64 * m;
+                    if (t < 8 * T2) {
+#pragma unroll
+                        for (int i = 0; i < F2MAX; ++i)
+                            if (i < F2) cw[i] = fmaf(drv[m], Qs[i * RS2 + LP2 + t], cw[i]);
+                    }
+                }
+                wave_reduce<F2MAX>(cw);                    // lane 16 r: sum[j + 4 r] in cw[j]
+                if (li == 0) {
+#pragma unroll
+                    for (int j = 0; j < F2MAX / 4; ++j) {
+                        const int i = j + (F2MAX / 4) * lk;
+                        if (i < F2) fz_add(prow + fc.W3 + o * F2 + i, cw[j], first);
+                    }
+                }
+            }
+            __syncthreads();                               // the q rows are read: dr may land on them
+            if (row_on) {
+                float* qrow = Qs + o * RS2 + LP2;
+#pragma unroll
+                for (int m = 0; m < MAXT1Q; ++m) {
+                    const int t = lane + 64 * m;
+                    if (t < T1) qrow[t] = drv[m];
+                }
+            }
+            __syncthreads();                               // dr rows complete
+            float dqv[MAXT1Q];
+            if (row_on) {
+                // dq[o,t] = sum_i W3[i,o] dr[i,t]
+                const float* w3c = prm + g.o_W3 + o;
+#pragma unroll
+                for (int m = 0; m < MAXT1Q; ++m) {
+                    const int t = lane + 64 * m;
+                    float a = 0.f;
+                    if (t < T1) {
+#pragma unroll
+                        for (int i = 0; i < F2MAX; ++i)
+                            if (i < F2) a = fmaf(w3c[i * F2], Qs[i * RS2 + LP2 + t], a);
+                    }
+                    dqv[m] = a;
+                }
+            }
+            __syncthreads();                               // dr rows read: dq may land on them
+            if (row_on) {
+                float* qrow = Qs + o * RS2 + LP2;
+#pragma unroll
+                for (int m = 0; m < MAXT1Q; ++m) {
+                    const int t = lane + 64 * m;
+                    if (t < T1) qrow[t] = dqv[m];
+                }
+                // dw2[o,k] += sum_t dq[o,t] d2[o,t+k-7]
+                const float* dr = D2s + o * RS2 + 1;
+                float cw[K2];
+#pragma unroll
+                for (int k = 0; k < K2; ++k) cw[k] = 0.f;
+#pragma unroll
+                for (int m = 0; m < MAXT1Q; ++m) {
+                    const int t = lane + 64 * m;
+                    if (t < T1) {
+#pragma unroll
+                        for (int k = 0; k < K2; ++k) cw[k] = fmaf(dqv[m], dr[t + k], cw[k]);
+                    }
+                }
+                wave_reduce<K2>(cw);
+                if (li == 0) {
+#pragma unroll
+                    for (int j = 0; j < K2 / 4; ++j)
+                        fz_add(prow + fc.w2 + o * K2 + j + (K2 / 4) * lk, cw[j], first);
+                }
+                wave_lds_fence();
+                // dd2[q] = sum_k w2[k] dq[q - k + 7]; dz2[4q + i] = dd2[q]/4 m2/(1-p) ELU'(z2[4q + i]);
+                // BN2 / BN1 sums; du = s2 dz2 over the v row
+                const float* qb = Qs + o * RS2 + (LP2 + 7);
+                float* vrow = Vs + o * RS + LP;
+                const unsigned i2 = ((unsigned)b * (unsigned)F2 + (unsigned)o) * (unsigned)T1;
+                for (int q = lane; q < T1; q += 64) {
+                    float a = 0.f;
+#pragma unroll
+                    for (int k = 0; k < K2; ++k) a = fmaf(w2[k], qb[q - k], a);
+                    a *= 0.25f * keep_mul(g, m2, key0, i2 + (unsigned)q);
+                    const floatx4 v = lds_ld4(vrow + 4 * q);
+                    floatx4 du;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float dz2 = a * elu_d(fmaf(al, v[i], be));
+                        aG2 = fmaf(dz2, fmaf(ax, v[i], bx), aG2);
+                        aB2 += dz2;
+                        const float d = s2 * dz2;
+                        aDV = fmaf(d, v[i], aDV);
+                        aSU += d;
+                        du[i] = d;
+                    }
+                    lds_st4(vrow + 4 * q, du);
+                }
+                // (samples [4 T1, T) of the v row are never written: du is zero there, as it has to be)
+                wave_lds_fence();
+                // dw1 raw correlation: sum_t du[o,t] s[o,t+k-P], 32 lags at a time
+                const float* srow = Ss + o * RS;
+                constexpr int NWC = (G_::OFF + 32 + 6) / 4;
+#pragma unroll
+                for (int kc = 0; kc < K1; kc += 32) {
+                    float c1w[32];
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) c1w[k] = 0.f;
+                    for (int q = lane; q < T1; q += 64) {
+                        float w[4 * NWC];
+                        lds_window<NWC>(srow + 4 * q + kc, w);
+                        const floatx4 du = lds_ld4(vrow + 4 * q);
+#pragma unroll
+                        for (int k = 0; k < 32; ++k)
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) c1w[k] = fmaf(du[i], w[G_::OFF + i + k], c1w[k]);
+                    }
+                    wave_reduce<32>(c1w);                  // lane 16 r: sum[j + 8 r] in c1w[j]
+                    if (li == 0) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) fz_add(prow + fc.w1 + o * K1 + kc + j + 8 * lk, c1w[j], first);
+                    }
+                }
+                wave_lds_fence();
+                // ds'[t] = sum_k w1[k] du[t - k + P]: the forward FIR with the taps flipped, pads R | P, over
+                // the s row (its last reader was the correlation above)
+                const float* row = Vs + o * RS;
+                float* dsrow = Ss + o * RS + LP;
+                // one or two quads past a multiple of 64 are 64-lane dot products instead, lane k on tap k
+                // (as k_infer_dx)
+                const int NQF = (TQ >= 64 && (TQ & 63) != 0 && (TQ & 63) <= 2) ? (TQ & ~63) : TQ;
+                for (int q = lane; q < NQF; q += 64) {
+                    float w[4 * G_::NW];
+                    lds_window<G_::NW>(row + 4 * q, w);
+                    floatx4 d;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        float a = 0.f;
+#pragma unroll
+                        for (int k = 0; k < K1; ++k) a = fmaf(tap[K1 - 1 - k], w[G_::OFFD + i + k], a);
+                        d[i] = 4 * q + i < T ? a : 0.f;
+                    }
+                    lds_st4(dsrow + 4 * q, d);
+                }
+                if (NQF < TQ) {
+                    for (int t = 4 * NQF; t < 4 * TQ; ++t) {
+                        float p = (lane < K1 && t < T) ? tapl * row[LP + t + G_::P - lane] : 0.f;
+                        p = wave_sum(p);
+                        if (lane == 0) dsrow[t] = p;
+                    }
+                }
+            }
+            __syncthreads();                               // ds' rows complete
+            // dws raw product sum_t ds'[o,t] x[c,t]: v_mfma_f32_16x16x4_f32, A = ds' tile (16 o x 4 t),
+            // B = x tile (4 t x 16 c), D[o = 4 (l >> 4) + r][c = 16 ct + (l & 15)]; wave w takes the
+            // 4-sample steps w, w + 16, ... and keeps its accumulators across the trials
+            for (int ks = wave; ks < TQ; ks += NWAVE) {
+                const int t = 4 * ks + lk;
+                const float av = li < F2 ? Ss[li * RS + LP + t] : 0.f;
+#pragma unroll
+                for (int ct = 0; ct < NCTM; ++ct) {
+                    if (ct < NCT) {
+                        const int c = 16 * ct + li;
+                        const float bv = c < C ? Xs[c * RS + LP + t] : 0.f;
+                        aWs[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, aWs[ct], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        __syncthreads();                                   // x rows read: the next trial's x may land
+        if (bnx < g.B) x_store<PF>(pf, C, T, RS, LP, Xs, tid);
+        __syncthreads();
+    }
+
+    if constexpr (BWD) {
+        // ---------------- publish this workgroup's partial row ----------------
+        aG3 = wave_sum(aG3); aB3 = wave_sum(aB3); aG2 = wave_sum(aG2); aB2 = wave_sum(aB2);
+        aDV = wave_sum(aDV); aSU = wave_sum(aSU);
+        if (row_on && lane == 0) {
+            prow[fc.g3 + o] = aG3; prow[fc.b3 + o] = aB3; prow[fc.g2 + o] = aG2; prow[fc.b2 + o] = aB2;
+            prow[fc.dv + o] = aDV; prow[fc.su + o] = aSU;
+        }
+        if (tid < NF) {
+#pragma unroll
+            for (int n = 0; n < NCLS; ++n) prow[fc.Wfc + n * NF + tid] = aFc[n];
+        }
+        if (tid == 0) {
+#pragma unroll
+            for (int n = 0; n < NCLS; ++n) prow[fc.bfc + n] = aBfc[n];
+            prow[fc.loss] = aLoss;
+        }
+        // the waves' dws accumulators summed in wave order through the (free) x rows
+        for (int w = 0; w < NWAVE; ++w) {
+            if (wave == w) {
+#pragma unroll
+                for (int ct = 0; ct < NCTM; ++ct) {
+                    if (ct < NCT) {
+#pragma unroll
+                        for (int rr = 0; rr < 4; ++rr) {
+                            const int oa = 4 * lk + rr, c = 16 * ct + li;
+                            if (oa < F2 && c < C) {
+                                const int i = oa * C + c;
+                                sm[i] = (w == 0 ? 0.f : sm[i]) + aWs[ct][rr];
+                            }
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < F2 * C; i += NTH) prow[fc.ws + i] = sm[i];
+    }
+}
+
+// Sum of the partial rows over the workgroups, in workgroup order and fp64, turned into `grads` (flat
+// parameter layout) and `loss`.  One output element per lane; the four waves of a workgroup take a
+// quarter of the rows each and their sums are added in row order, so the result is a function of the
+// partial rows alone.
+constexpr int NTFR = 256, FR_OUT = 64;
+__global__ __launch_bounds__(NTFR) void k_frozen_reduce(Geo g, const float* __restrict__ prm,
+                                                        const float* __restrict__ bn,
+                                                        const float* __restrict__ part, int nrows,
+                                                        float* __restrict__ grads, float* __restrict__ loss) {
+    __shared__ double sh[NTFR / FR_OUT][FR_OUT];
+    const FzCols fc = fz_cols(g);
+    const int tid = threadIdx.x, le = tid & (FR_OUT - 1), qd = tid / FR_OUT;
+    const int e = blockIdx.x * FR_OUT + le;
+    const int w0 = (int)((long long)qd * nrows / (NTFR / FR_OUT)), w1 = (int)((long long)(qd + 1) * nrows / (NTFR / FR_OUT));
+    auto col = [&](int c) {
+        double s = 0.0;
+        const float* p = part + c;
+#pragma unroll 8
+        for (int w = w0; w < w1; ++w) s += (double)p[(size_t)w * fc.n];
+        return s;
+    };
+    auto Wsum = [&](int o) {
+        double W = 0.0;
+        for (int c = 0; c < g.C; ++c) W += (double)prm[g.o_ws + o * g.C + c];
+        return W;
+    };
+    auto inv1 = [&](int gq) { return 1.0 / sqrt((double)bn[g.F1 + gq] + (double)g.eps); };
+    double acc = 0.0;
+    if (e <= g.nparam) {
+        if (e < g.o_g1) {                                  // temporal.0.weight [F1][K1]
+            const int gq = e / g.K1, k = e - gq * g.K1;
+            for (int d = 0; d < g.D; ++d) acc += col(fc.w1 + (gq * g.D + d) * g.K1 + k);
+            acc *= (double)prm[g.o_g1 + gq] * inv1(gq);
+        } else if (e < g.o_b1) {                           // temporal.1.weight [F1]
+            const int gq = e - g.o_g1;
+            for (int d = 0; d < g.D; ++d) {
+                const int o = gq * g.D + d;
+                acc += col(fc.dv + o) - (double)bn[gq] * Wsum(o) * col(fc.su + o);
+            }
+            acc *= inv1(gq);
+        } else if (e < g.o_ws) {                           // temporal.1.bias [F1]
+            const int gq = e - g.o_b1;
+            for (int d = 0; d < g.D; ++d) {
+                const int o = gq * g.D + d;
+                acc += Wsum(o) * col(fc.su + o);
+            }
+        } else if (e < g.o_g2) {                           // spatial.weight [F2][C]
+            const int i = e - g.o_ws, o = i / g.C, gq = o / g.D;
+            const double a1 = (double)prm[g.o_g1 + gq] * inv1(gq);
+            const double c1 = (double)prm[g.o_b1 + gq] - a1 * (double)bn[gq];
+            acc = a1 * col(fc.ws + i) + c1 * col(fc.su + o);
+        } else if (e < g.o_b2) acc = col(fc.g2 + (e - g.o_g2));
+        else if (e < g.o_w2) acc = col(fc.b2 + (e - g.o_b2));
+        else if (e < g.o_W3) acc = col(fc.w2 + (e - g.o_w2));
+        else if (e < g.o_g3) acc = col(fc.W3 + (e - g.o_W3));
+        else if (e < g.o_b3) acc = col(fc.g3 + (e - g.o_g3));
+        else if (e < g.o_Wfc) acc = col(fc.b3 + (e - g.o_b3));
+        else if (e < g.o_bfc) acc = col(fc.Wfc + (e - g.o_Wfc));
+        else if (e < g.nparam) acc = col(fc.bfc + (e - g.o_bfc));
+        else acc = col(fc.loss);
+    }
+    sh[qd][le] = acc;
+    __syncthreads();
+    if (qd == 0 && e <= g.nparam) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < NTFR / FR_OUT; ++j) s += sh[j][le];
+        float v = (float)s;
+        if (e == g.nparam) {
+            if (loss) *loss = v;
+        } else {
+            if (!g.noclamp) {
+                if (e >= g.o_ws && e < g.o_g2) v = fminf(fmaxf(v, -1.0f), 1.0f);             // model.py:44
+                else if (e >= g.o_Wfc && e < g.o_bfc) v = fminf(fmaxf(v, -0.25f), 0.25f);    // model.py:84
+            }
+            grads[e] = v;
+        }
+    }
+}
+
+}  // namespace eeg

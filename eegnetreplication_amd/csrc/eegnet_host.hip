@@ -359,6 +359,8 @@ static void set_attrs_shape() {
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_infer<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_infer_dx<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 template <int K1>
@@ -1023,6 +1025,99 @@ int eegnet_stage_sums(const eegnet_dims* dims, int pass, size_t* offset_bytes, i
     const int n[TK_COUNT] = {g.nA, g.nB, g.nC, g.nD, g.nE};
     *count = n[pass];
     return 0;
+}
+
+}  // extern "C"
+
+// ---- frozen-BatchNorm fine-tuning (eegnet_frozen.hip) ----
+// the checks eegnet_forward_frozen and eegnet_frozen_step share; none needs a GPU
+static int frozen_geo(const eegnet_dims* dims, Geo* g) {
+    if (int r = make_geo(dims, g, false)) return r;
+    if (g->wide) return fail(EEGNET_EINVAL, "frozen BatchNorm: F1*D = %d > 16 is not supported", g->F2);
+    if (int r = make_geo(dims, g)) return r;
+    if (g->XP != g->T) return fail(EEGNET_EINVAL, "frozen BatchNorm takes x as [B][C][T] (x_pitch 0 or T)");
+    // k_frozen runs in k_infer_dx's LDS plan: x, s (then ds'), v (then du), the block-2 rows, h, logits
+    if (g->ldsX * 4 > LDS_MAX)
+        return fail(EEGNET_EINVAL, "frozen BatchNorm: dims need %d B of LDS (> %d)", g->ldsX * 4, LDS_MAX);
+    if (g->NF > NTH) return fail(EEGNET_EINVAL, "frozen BatchNorm: F2*(T/32) = %d > %d", g->NF, NTH);
+    return 0;
+}
+
+static size_t frozen_ws_bytes(const Geo& g) { return rupz((size_t)g.grid * fz_cols(g).n * 4, 256); }
+
+static void frozen_launch(const Geo& g, bool bwd, const float* params, const float* bn, const float* x,
+                          const float* dlogits, const int64_t* labels, const uint8_t* m2, const uint8_t* m3,
+                          float* logits, float* part, hipStream_t s) {
+#define LAUNCH_FZ(K, CC, TT, FF) if (bwd) hipLaunchKernelGGL((k_frozen<K, CC, TT, FF, true>), dim3(g.grid), dim3(NTH), g.ldsX * 4, s, \
+                                                   g, params, bn, x, dlogits, labels, m2, m3, logits, part); \
+    else hipLaunchKernelGGL((k_frozen<K, CC, TT, FF, false>), dim3(g.grid), dim3(NTH), g.ldsX * 4, s, \
+                                                   g, params, bn, x, dlogits, labels, m2, m3, logits, part)
+    if (g.K1 == 32) EEG_DISPATCH(32, g, LAUNCH_FZ); else EEG_DISPATCH(64, g, LAUNCH_FZ);
+}
+
+extern "C" {
+
+int eegnet_frozen_workspace_bytes(const eegnet_dims* dims, size_t* out) {
+    Geo g;
+    if (int r = frozen_geo(dims, &g)) return r;
+    if (!out) return fail(EEGNET_EINVAL, "out is NULL");
+    *out = frozen_ws_bytes(g);
+    return 0;
+}
+
+int eegnet_forward_frozen(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                          const float* x, const uint8_t* mask2, const uint8_t* mask3, uint64_t seed,
+                          uint64_t offset, float* logits, void* stream) {
+    Geo g;
+    if (int r = frozen_geo(dims, &g)) return r;
+    if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
+    if (int r = check_ptrs(x, "x", logits, "logits")) return r;
+    if ((g.T & 3) == 0 && ((uintptr_t)x & 15)) return fail(EEGNET_EINVAL, "frozen BatchNorm: x must be 16-byte aligned");
+    g.drop = g.p > 0.f ? 1 : 0;
+    set_key(&g, seed, offset);
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    frozen_launch(g, false, params, bn_buffers, x, nullptr, nullptr, mask2, mask3, logits, nullptr, s);
+    LAUNCH_CHECK("k_frozen(fwd)");
+    return 0;
+}
+
+int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,
+                       const float* dlogits, const int64_t* labels, const uint8_t* mask2,
+                       const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads,
+                       float* adam_state, int32_t* step, float lr, float beta1, float beta2, float eps,
+                       float* loss, float* logits, void* ws, void* stream, int flags) {
+    Geo g;
+    if (int r = frozen_geo(dims, &g)) return r;
+    if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
+    if (int r = check_ptrs(x, "x", grads, "grads")) return r;
+    if (int r = check_ptrs(ws, "ws")) return r;
+    if (!dlogits && !labels) return fail(EEGNET_EINVAL, "frozen step: need dlogits or labels");
+    if (dlogits && labels) return fail(EEGNET_EINVAL, "frozen step: dlogits and labels are exclusive");
+    if (adam_state && !step) return fail(EEGNET_EINVAL, "step is NULL");
+    if (flags & ~(EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP))
+        return fail(EEGNET_EINVAL, "frozen step: unknown flags 0x%x", flags & ~(EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP));
+    if ((g.T & 3) == 0 && ((uintptr_t)x & 15)) return fail(EEGNET_EINVAL, "frozen BatchNorm: x must be 16-byte aligned");
+    g.noclamp = (flags & EEGNET_NO_CLAMP) ? 1 : 0;
+    g.drop = g.p > 0.f ? 1 : 0;
+    set_key(&g, seed, offset);
+    if (flags & EEGNET_KEY_FROM_STEP) {
+        if (!step) return fail(EEGNET_EINVAL, "EEGNET_KEY_FROM_STEP needs the device step counter");
+        g.keystep = step; g.kseed = seed; g.koff = offset;
+    }
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    float* part = (float*)ws;
+    frozen_launch(g, true, params, bn_buffers, x, dlogits, labels, mask2, mask3, logits, part, s);
+    LAUNCH_CHECK("k_frozen");
+    hipLaunchKernelGGL(k_frozen_reduce, dim3((g.nparam + 1 + FR_OUT - 1) / FR_OUT), dim3(NTFR), 0, s, g,
+                       (const float*)params, bn_buffers, (const float*)part, g.grid, grads, loss);
+    LAUNCH_CHECK("k_frozen_reduce");
+    if (!adam_state) return 0;
+    // the Adam kernel of eegnet_adam_step behind the reduction; it advances the step counter last, after
+    // k_frozen has read it for the dropout key (EEGNET_KEY_FROM_STEP)
+    return eegnet_adam_step(g.nparam, params, grads, adam_state, adam_state + g.nparam, step, lr, beta1, beta2,
+                            eps, stream);
 }
 
 }  // extern "C"

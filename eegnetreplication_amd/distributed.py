@@ -53,6 +53,15 @@ def allreduce_mean_(t: torch.Tensor, group=None) -> torch.Tensor:
     return t
 
 
+def _refuse_frozen(model):
+    """The data-parallel and synchronised-BatchNorm steps run batch statistics only: a model with frozen
+    BatchNorm layers (EEGNet.freeze_bn) would silently train with them and move its running ones."""
+    if getattr(model, "bn_frozen", False):
+        raise ValueError("DataParallelTrainer does not support a model with frozen BatchNorm "
+                         "(EEGNet.freeze_bn): fine-tune it with train() / FusedTrainer, or call "
+                         "freeze_bn(False)")
+
+
 class DataParallelTrainer:
     """Fused HIP train step + ONE collective per step (cfg4).
 
@@ -86,6 +95,7 @@ class DataParallelTrainer:
 
     def __init__(self, model: EEGNet, lr=1e-3, betas=(0.9, 0.999), eps=1e-7, group=None,
                  broadcast_buffers=True, sync_bn=False):
+        _refuse_frozen(model)
         self.model = model
         self.sync_bn = bool(sync_bn)
         if self.sync_bn and model.shape.F2 > 16:
@@ -212,6 +222,7 @@ class DataParallelTrainer:
         return sums
 
     def step_sync_bn(self, x, y):
+        _refuse_frozen(self.model)
         self._step += 1
         seed = 0x5EED_0000 + self._step
         offset = self._step * self.world + self.rank
@@ -226,6 +237,7 @@ class DataParallelTrainer:
     def step(self, x, y):
         if self.sync_bn:
             return self.step_sync_bn(x, y)
+        _refuse_frozen(self.model)
         self._step += 1
         seed = 0x5EED_0000 + self._step
         offset = self._step * self.world + self.rank        # distinct masks on every rank

@@ -35,6 +35,14 @@ class _FoldGraph:
         self.perm, self.losses, self.graph = perm, losses, graph
 
 
+def _refuse_frozen(models):
+    """Fold batching runs the batch-statistics step only: a model with frozen BatchNorm layers
+    (EEGNet.freeze_bn) would silently train with batch statistics and move its running ones."""
+    if any(getattr(m, "bn_frozen", False) for m in models):
+        raise ValueError("FoldBatch does not support models with frozen BatchNorm (EEGNet.freeze_bn): "
+                         "fine-tune them with train() / FusedTrainer, or call freeze_bn(False)")
+
+
 class FoldBatch:
     """k independent fold runs on one GPU, one HIP stream each.
 
@@ -58,6 +66,7 @@ class FoldBatch:
         table (and, at 22 x 257, the padded copy the kernels read) keeps the old trials."""
         if len(models) != len(seeds) or not models:
             raise ValueError("need one seed per model and at least one model")
+        _refuse_frozen(models)
         dev = models[0].flat_parameters().device
         if dev.type != "cuda":
             raise RuntimeError("FoldBatch runs on a HIP device only")
@@ -252,6 +261,7 @@ class FoldBatch:
         (the reference's running loss, model.py:150).  Nothing is synchronised."""
         if len(data) != len(self.models):
             raise ValueError("one (X, y) per fold")
+        _refuse_frozen(self.models)
         if self.fused and all(X.shape[0] == data[0][0].shape[0] for X, _ in data):
             return self._epoch_fused(data, batch_size, generators)
         cur = torch.cuda.current_stream()

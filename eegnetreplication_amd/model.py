@@ -11,6 +11,10 @@ cadence and the F4 "best model aliases the live weights" behaviour), with the ep
 accuracy accumulated on the device (one host sync per epoch instead of one per batch).  When the
 optimizer is ``torch.optim.Adam`` and the loss is a default ``nn.CrossEntropyLoss`` the whole step
 (forward, CE, backward, clamps, Adam) runs as one fused device sequence.
+
+``model.freeze_bn()`` switches the train-mode forward / backward and the fused step to frozen
+BatchNorm (running statistics used and left untouched, dropout on) for fine-tuning a trained model
+on a few calibration trials: one fused trial-parallel launch instead of the five passes.
 """
 
 from __future__ import annotations
@@ -55,6 +59,7 @@ class EEGNet(nn.Module):
         self.C, self.T, self.F1, self.D, self.K1 = C, T, F1, D, K1
         self._masks = None
         self._rng_offset = 0
+        self.bn_frozen = False
         self._flatten()
 
     # -- flat device layout -----------------------------------------------------------------
@@ -187,6 +192,17 @@ class EEGNet(nn.Module):
                                             p=key[0], eps=key[1], momentum=key[2]))
         return self._shape_cache[1]
 
+    # -- frozen BatchNorm (fine-tuning) ---------------------------------------------------------
+    def freeze_bn(self, mode: bool = True):
+        """Freeze (or release) the three BatchNorm layers for fine-tuning, as ``bn.eval()`` on a stock
+        module: while set and the model is in train mode, the forward normalises with the running
+        statistics and writes neither them nor ``num_batches_tracked``; dropout stays on and
+        ``backward()`` fills all 12 ``param.grad`` (one fused launch, F1*D <= 16).  A plain attribute
+        (``bn_frozen``), not a buffer: ``train()`` / ``eval()`` / ``to()`` leave it alone, it is not in
+        ``state_dict``, and it has no effect in eval mode.  Returns self."""
+        self.bn_frozen = bool(mode)
+        return self
+
     # -- dropout control (test hook) ------------------------------------------------------------
     def set_dropout_masks(self, m2, m3):
         """Inject keep-masks ([B,F2,T//4], [B,F2,T//128] uint8, 1 = keep) for the train-mode
@@ -236,6 +252,8 @@ class EEGNet(nn.Module):
             masks = self._masks
             if masks is not None and masks[0].shape[0] != x.shape[0]:
                 raise RuntimeError("injected dropout masks do not match the batch size")
+            if getattr(self, "bn_frozen", False):
+                return _FrozenTrainFn.apply(x, self, shape, seed, offset, masks, *params)
             return _TrainFn.apply(x, self, shape, seed, offset, masks, *params)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             return _EvalFn.apply(x, self, shape, *params)
@@ -262,6 +280,48 @@ class _TrainFn(torch.autograd.Function):
         x, ws, flat = ctx.saved_tensors
         g = ops.backward(ctx.shape, flat, x, ws, ctx.seed, ctx.offset,
                          dlogits=dlogits.contiguous().float(), masks=ctx.masks)
+        out, o = [], 0
+        for s in ctx.param_shapes:
+            k = 1
+            for d in s:
+                k *= d
+            out.append(g[o:o + k].view(s))
+            o += k
+        return (None, None, None, None, None, None, *out)
+
+
+def _not_supported(e: RuntimeError):
+    """The library's "... is not supported" rejections (wide dims) as NotImplementedError."""
+    if "is not supported" in str(e):
+        raise NotImplementedError(str(e)) from None
+    raise e
+
+
+class _FrozenTrainFn(torch.autograd.Function):
+    """Train-mode step with the BatchNorm layers frozen (EEGNet.freeze_bn) as one autograd node:
+    forward = the forward-only variant of the fused frozen kernel, backward(dlogits) = one
+    eegnet_frozen_step (gradients clamped as model.py:44,84, no Adam).  The backward differentiates the
+    forward that ran: parameters, running statistics, masks and dropout key are those of forward time."""
+
+    @staticmethod
+    def forward(ctx, x, mod, shape, seed, offset, masks, *params):
+        flat = mod.flat_parameters().clone()
+        bn_flat = mod.flat_bn_buffers().clone()
+        try:
+            logits = ops.forward_frozen(shape, flat, bn_flat, x, seed, offset, masks=masks)
+        except RuntimeError as e:
+            _not_supported(e)
+        ctx.shape, ctx.seed, ctx.offset, ctx.masks = shape, seed, offset, masks
+        ctx.param_shapes = [p.shape for p in params]
+        ctx.save_for_backward(x, flat, bn_flat)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        x, flat, bn_flat = ctx.saved_tensors
+        ws = ops.new_frozen_workspace(ctx.shape, x.shape[0], x.device)
+        g = ops.frozen_step(ctx.shape, flat, bn_flat, x, ctx.seed, ctx.offset, torch.empty_like(flat), ws,
+                            dlogits=dlogits.contiguous().float(), masks=ctx.masks)
         out, o = [], 0
         for s in ctx.param_shapes:
             k = 1
@@ -436,6 +496,7 @@ class FusedTrainer:
         dev = model.flat_parameters().device
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self._ws = {}
+        self._fws = {}
 
     def workspace(self, B):
         ws = self._ws.get(B)
@@ -444,10 +505,31 @@ class FusedTrainer:
             self._ws[B] = ws
         return ws
 
+    def frozen_workspace(self, B):
+        ws = self._fws.get(B)
+        if ws is None:
+            ws = ops.new_frozen_workspace(self.model.shape, B, self.model.flat_parameters().device)
+            self._fws[B] = ws
+        return ws
+
     def step(self, x, y, logits=None):
         m = self.model
         seed, offset = m.next_dropout_key()
         flat, bn_flat, nbt = m.flat_views()
+        if getattr(m, "bn_frozen", False):
+            # frozen BatchNorm (EEGNet.freeze_bn): one trial-parallel launch, the reduction and Adam; the
+            # running statistics and num_batches_tracked are not touched
+            masks = m._masks
+            if masks is not None and masks[0].shape[0] != x.shape[0]:
+                raise RuntimeError("injected dropout masks do not match the batch size")
+            try:
+                ops.frozen_step(m.shape, flat, bn_flat, x.contiguous(), seed, offset, self.adam.grads,
+                                self.frozen_workspace(x.shape[0]), labels=y, masks=masks,
+                                adam_state=self.adam.state, step_i32=self.adam.step, loss=self.loss,
+                                logits=logits, lr=self.lr, betas=self.betas, eps=self.eps)
+            except RuntimeError as e:
+                _not_supported(e)
+            return self.loss
         ops.train_step(m.shape, flat, bn_flat, x, y, seed, offset,
                        self.adam.grads, self.adam.state, self.adam.step, self.workspace(x.shape[0]),
                        self.loss, logits=logits, lr=self.lr, betas=self.betas, eps=self.eps,

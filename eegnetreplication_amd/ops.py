@@ -192,6 +192,48 @@ def input_grad_eval(shape: Shape, flat_params, bn_flat, x, *, kind, dlogits=None
     return out, logits
 
 
+def new_frozen_workspace(shape: Shape, B: int, device) -> torch.Tensor:
+    """Workspace of ``frozen_step`` for batches of B trials (eegnet_frozen_workspace_bytes)."""
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load().eegnet_frozen_workspace_bytes(ctypes.byref(shape.dims(B)), ctypes.byref(out)),
+               "eegnet_frozen_workspace_bytes")
+    return torch.zeros(int(out.value), dtype=torch.uint8, device=device)
+
+
+def forward_frozen(shape: Shape, flat_params, bn_flat, x, seed: int, offset: int, masks=None,
+                   p: float | None = None) -> torch.Tensor:
+    """Train-mode forward with the BatchNorm layers frozen (eegnet_forward_frozen): running statistics
+    used and not written, dropout from ``masks`` or the (seed, offset) generator."""
+    x = x.contiguous()
+    B = x.shape[0]
+    logits = torch.empty((B, NCLS), dtype=torch.float32, device=x.device)
+    m2, m3 = masks if masks is not None else (None, None)
+    _lib.check(_lib.load().eegnet_forward_frozen(
+        ctypes.byref(shape.dims(B, p)), _ptr(flat_params), _ptr(bn_flat), _ptr(x), _ptr(m2), _ptr(m3),
+        ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(logits), _stream()), "eegnet_forward_frozen")
+    return logits
+
+
+def frozen_step(shape: Shape, flat_params, bn_flat, x, seed: int, offset: int, grads, ws, *, dlogits=None,
+                labels=None, masks=None, adam_state=None, step_i32=None, loss=None, logits=None, lr=1e-3,
+                betas=(0.9, 0.999), eps=1e-7, p: float | None = None, clamp=True, key_from_step=False):
+    """One frozen-BatchNorm iteration (eegnet_frozen_step) on the device, no host sync: forward, the
+    seed (``dlogits`` [B, 4], or mean cross-entropy against ``labels`` with the loss written to
+    ``loss``), backward and all 12 parameter gradients into ``grads``; with ``adam_state`` the Adam
+    update follows on the same stream.  ``x`` must be contiguous [B, C, T]; ``ws`` from
+    ``new_frozen_workspace``."""
+    if not x.is_contiguous():
+        raise ValueError("frozen_step takes a contiguous [B, C, T] x")
+    m2, m3 = masks if masks is not None else (None, None)
+    _lib.check(_lib.load().eegnet_frozen_step(
+        ctypes.byref(shape.dims(x.shape[0], p)), _ptr(flat_params), _ptr(bn_flat), _ptr(x), _ptr(dlogits),
+        _ptr(labels), _ptr(m2), _ptr(m3), ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(grads),
+        _ptr(adam_state), _ptr(step_i32), ctypes.c_float(lr), ctypes.c_float(betas[0]),
+        ctypes.c_float(betas[1]), ctypes.c_float(eps), _ptr(loss), _ptr(logits), _ptr(ws), _stream(),
+        (0 if clamp else NO_CLAMP) | (KEY_FROM_STEP if key_from_step else 0)), "eegnet_frozen_step")
+    return grads
+
+
 def forward_eval_bf16(shape: Shape, flat_params, bn_flat, x) -> torch.Tensor:
     """Eval-mode forward on bf16 input (bf16 MFMA operands, fp32 accumulation, fp32 logits)."""
     if x.dtype != torch.bfloat16:

@@ -7,6 +7,7 @@
  *   optimizer.step() (Adam)   src/eegnet_repl/train.py:94-101, model.py:148 -> eegnet_adam_step
  *   one hot-loop iteration    src/eegnet_repl/model.py:136-148 -> eegnet_train_step
  *   saliency / x.grad in .eval() (plain autograd on the nn.Module) -> eegnet_input_grad_eval
+ *   the hot loop with bn.eval() on the three BatchNorm2d (fine-tuning) -> eegnet_frozen_step
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer (hipMalloc / torch CUDA tensor) unless noted.  The library never
@@ -127,6 +128,33 @@ enum { EEGNET_SEED_DLOGITS = 0,  /* g = dlogits[b]                              
 int eegnet_input_grad_eval(const eegnet_dims* dims, const float* params, const float* bn_buffers,
                            const float* x, int seed_kind, const float* dlogits,
                            const int64_t* targets, float* dx, float* logits, void* stream);
+
+/* Frozen-BatchNorm fine-tuning: train mode with the three BatchNorm layers frozen, as bn.eval() on a
+ * stock module -- running statistics used and never written (bn_buffers is const, there is no
+ * num_batches_tracked argument), dropout applied as in the train path (masks or the (seed, offset)
+ * generator).  Every trial is then independent: one fused kernel runs forward, loss, backward and all
+ * 12 parameter gradients of a trial on one CU and leaves one partial row per workgroup in `ws`; a small
+ * second kernel sums the rows in workgroup order (fp64), clamps and writes `grads` / `loss`.  No
+ * atomics: the same inputs give the same bits.  F1*D <= 16 only, x_pitch 0 or T, x 16-byte aligned when
+ * T % 4 == 0; the shapes eegnet_input_grad_eval takes.  The validation needs no GPU.
+ *
+ * eegnet_frozen_workspace_bytes: bytes of `ws` (the partial rows; zero-fill it once, as the other
+ * workspaces).
+ * eegnet_forward_frozen: the logits alone (the autograd forward).
+ * eegnet_frozen_step: exactly one of dlogits [B,4] (autograd) and labels (mean cross-entropy; the loss
+ * goes to `loss`, device fp32, nullable).  adam_state == NULL stops after the gradients; otherwise the
+ * Adam kernel of eegnet_adam_step is enqueued behind the reduction on the same stream (adam_state, step
+ * as for eegnet_train_step).  flags: EEGNET_NO_CLAMP, EEGNET_KEY_FROM_STEP (needs step); any other bit
+ * is EEGNET_EINVAL.  logits is nullable.  No host synchronisation: capturable in a hipGraph. */
+int eegnet_frozen_workspace_bytes(const eegnet_dims* dims, size_t* out);
+int eegnet_forward_frozen(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                          const float* x, const uint8_t* mask2, const uint8_t* mask3, uint64_t seed,
+                          uint64_t offset, float* logits, void* stream);
+int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,
+                       const float* dlogits, const int64_t* labels, const uint8_t* mask2,
+                       const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads,
+                       float* adam_state, int32_t* step, float lr, float beta1, float beta2, float eps,
+                       float* loss, float* logits, void* ws, void* stream, int flags);
 
 /* bf16 batched eval-mode forward (BASELINE cfg5, EEGNet-16,4 at 64ch x 512):
  * the same function as eegnet_forward_eval (model.py:91-99 in .eval(), called at model.py:161/220,
