@@ -197,13 +197,24 @@ enum PassCMode { PC_LOGITS = 1, PC_BWD = 2, PC_CE = 4 };
 
 // In-kernel reduction + finalize (eegnet_finalize.hip): every pass kernel ends with a ticketed
 // two-level fp64 reduction of its per-workgroup partial rows; the last workgroup to arrive runs that
-// pass's finalize.  Ticket words: NCNT per pass, zeroed by a memset node at the start of every call.
+// pass's finalize.  Ticket words: NCNT per pass, zero in a new workspace; every reduction re-arms its own
+// when it ends, and pass A clears those of the later passes of its call.
 constexpr int KSMAX = 16;       // ws MFMA k-steps: ceil(C / 4), C <= 64
 #ifndef EEGNET_NGRPMAX
 #define EEGNET_NGRPMAX 16
 #endif
 constexpr int NGRPMAX = EEGNET_NGRPMAX;   // groups <= NCNT - 1 (ticket words)
 constexpr int NCNT = 40;
+// Ticket words sit TKS words (256 bytes) apart (tkw).  Workgroups that end their loops together (pass C
+// at B = 4096: one trial per wave, 256 workgroups within a microsecond) otherwise queue their agent-scope
+// atomics on the eight group words of ONE 128-byte line: the last group's ticket came 2.3-2.5 us after
+// the last publish there (0.6 us in the passes whose workgroups arrive spread out), 1.1 us with the
+// words apart (-DEEGNET_TKS=1: adjacent words, for A/B runs).
+#ifndef EEGNET_TKS
+#define EEGNET_TKS 64
+#endif
+constexpr int TKS = EEGNET_TKS;
+__host__ __device__ __forceinline__ unsigned* tkw(unsigned* cnt, int i) { return cnt + (size_t)i * TKS; }
 constexpr int SPLIT_COLS = 2048;  // wide passes with more partial-row columns reduce in k_coltail          // [0, ngrp) group tickets, [NCNT-1] the top-level ticket
 constexpr int TK_PASSES = 5;      // ticket blocks: passes A..E, contiguous from pass A's
 struct FinArgs {
@@ -301,7 +312,7 @@ __device__ __forceinline__ FinArgs fold_fin(const FoldCall& fc, const eegnet_fol
     char* ws = (char*)f.ws;
     FinArgs a;
     a.part2 = (double*)(ws + fc.off.sums);
-    a.cnt = (unsigned*)(ws + fc.off.cnt) + tk * NCNT;
+    a.cnt = tkw((unsigned*)(ws + fc.off.cnt), tk * NCNT);
     a.stats = (double*)(ws + fc.off.stats);
     a.coef = (float*)(ws + fc.off.coef);
     a.bn = f.bn_buffers;

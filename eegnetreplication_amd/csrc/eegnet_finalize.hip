@@ -98,7 +98,7 @@ __device__ bool grid_reduce(const Geo& g, const float* part, int ncols, const Fi
     const int r0 = grp * rgs, r1 = min(grid, r0 + rgs);
     const int tp = fa.tpass;
     TRACE(g, tp, TR_PUB);
-    if (!take_ticket(fa.cnt + grp, (unsigned)(r1 - r0), flag)) return false;
+    if (!take_ticket(tkw(fa.cnt, grp), (unsigned)(r1 - r0), flag)) return false;
     TRACE_FS(g, tp, 0);            // last writer wins: about the last group
     if (flat) {
         // thread (column c, phase ph) sums rows ph, ph + FLAT_PH, ... in order; the phases are then
@@ -173,7 +173,7 @@ __device__ bool grid_reduce(const Geo& g, const float* part, int ncols, const Fi
     }
     TRACE(g, tp, TR_GRP);
     TRACE_FS(g, tp, 1);            // last writer wins: about the last group
-    if (!take_ticket(fa.cnt + (NCNT - 1), (unsigned)ngrp, flag)) return false;
+    if (!take_ticket(tkw(fa.cnt, NCNT - 1), (unsigned)ngrp, flag)) return false;
     TRACE_FS(g, tp, 2);
     for (int c = tid; c < ncols; c += nth) {
         double v[NGRPMAX];
@@ -186,8 +186,8 @@ __device__ bool grid_reduce(const Geo& g, const float* part, int ncols, const Fi
     }
     TRACE_FS(g, tp, 9);
     // every ticket of this pass has been taken: re-arm them for the next call
-    if (tid < ngrp) __hip_atomic_store(fa.cnt + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) __hip_atomic_store(fa.cnt + (NCNT - 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid < ngrp) __hip_atomic_store(tkw(fa.cnt, tid), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) __hip_atomic_store(tkw(fa.cnt, NCNT - 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     TRACE_FS(g, tp, 10);
     __syncthreads();
     TRACE(g, tp, TR_TOP);
@@ -760,10 +760,10 @@ __global__ __launch_bounds__(NTCT) void k_coltail(Geo gin, const float* prm, con
         for (int k = 0; k < NPH; ++k) t += ph[k * 64 + lane];
         pub(fa.part2 + c, t);
     }
-    if (!take_ticket(fa.cnt + (NCNT - 1), gridDim.x, (int*)dsmt)) return;
+    if (!take_ticket(tkw(fa.cnt, NCNT - 1), gridDim.x, (int*)dsmt)) return;
     double* S = dsmt + 2;
     stage_pub<8>(S, fa.part2, ncols);
-    if (tid == 0) __hip_atomic_store(fa.cnt + (NCNT - 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) __hip_atomic_store(tkw(fa.cnt, NCNT - 1), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if constexpr (FIN == 3) fin3(g, prm, S, fa);
     else if constexpr (FIN == 4) fin4(g, prm, S, fa);

@@ -23,7 +23,7 @@ constexpr int LDS_MAX = 160 * 1024 - 256;
 static inline int rup(int a, int m) { return (a + m - 1) / m * m; }
 static inline size_t rupz(size_t a, size_t m) { return (a + m - 1) / m * m; }
 
-constexpr size_t CNT_BYTES = (size_t)TK_COUNT * NCNT * 4;     // 800 B, a multiple of 16
+constexpr size_t CNT_BYTES = (size_t)TK_COUNT * NCNT * TKS * 4;     // a multiple of 16
 
 struct WsLayout {
     size_t cnt, partA, partB, partC, partD, partE, sums, stats, coef, d2, E1, E2, dp2, dl, s, v, q3, r3;
@@ -260,7 +260,9 @@ static WsLayout make_layout(const Geo& g) {
     WsLayout L;
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = rupz(o + bytes, 256); return r; };
-    L.cnt = take(CNT_BYTES);          // ticket words first: the per-call memset covers [0, CNT_BYTES)
+    // ticket words first: zero when the workspace is allocated (ops.new_workspace), re-armed by each pass's
+    // reduction when it ends and, for the later passes of a call, cleared again by pass A
+    L.cnt = take(CNT_BYTES);
     L.partA = take((size_t)std::max(g.gridS, g.gridA) * g.nA * 4);
     L.partB = take((size_t)std::max(std::max(g.gridS, g.grid), g.gridW2) * g.nB * 4);
     L.partC = take((size_t)std::max(std::max(g.grid, g.gridB2), g.gridW2) * g.nC * 4);
@@ -413,7 +415,7 @@ static FinArgs fin_args(const WsLayout& L, char* ws, int tk, float* bn, float* g
     FinArgs f;
     memset(&f, 0, sizeof(f));
     f.part2 = (double*)(ws + L.sums);
-    f.cnt = (unsigned*)(ws + L.cnt) + tk * NCNT;
+    f.cnt = tkw((unsigned*)(ws + L.cnt), tk * NCNT);
     f.stats = (double*)(ws + L.stats);
     f.coef = (float*)(ws + L.coef);
     f.bn = bn; f.grads = grads; f.loss = loss;

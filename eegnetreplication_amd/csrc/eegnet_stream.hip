@@ -260,7 +260,7 @@ __device__ __forceinline__ void pass_a_body(const Geo& g, const float* __restric
     // every pass re-arms its own tickets when it finishes; pass A also clears those of the later
     // passes of this call (stream order), so a call never depends on how the previous one ended
     if (blockIdx.x == 0 && threadIdx.x < (TK_PASSES - 1) * NCNT)
-        __hip_atomic_store(fa.cnt + NCNT + threadIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(tkw(fa.cnt, NCNT + threadIdx.x), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     constexpr int NTS = FF ? 1 : RPW;
     constexpr int NEI = G_::template nei<NTB>();
     const int D = FF ? 2 : g.D;

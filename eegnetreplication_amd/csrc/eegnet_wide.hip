@@ -170,7 +170,7 @@ __global__ __launch_bounds__(NTW) void k_wpass_a(Geo gin, const float* __restric
     constexpr int NEI = G_::template nei<NTW>();
     const int C = g.C, T = g.T, F2 = g.F2, RS = g.RS, TQ = (T + 3) >> 2, NT16 = (T + 15) >> 4;
     if (blockIdx.x == 0 && threadIdx.x < (TK_PASSES - 1) * NCNT)
-        __hip_atomic_store(fa.cnt + NCNT + threadIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(tkw(fa.cnt, NCNT + threadIdx.x), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     int j, b0, b1;
     wide_unit(g, j, b0, b1);
