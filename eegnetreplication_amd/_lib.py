@@ -25,6 +25,13 @@ class Fold(ctypes.Structure):
                [("seed", ctypes.c_uint64), ("xstat", ctypes.c_void_p)]
 
 
+class EvalFold(ctypes.Structure):
+    """Mirror of ``eegnet_eval_fold`` (include/eegnet_abi.h): one model of a fold-indexed validation call."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("params", "bn_buffers", "x", "labels")] + \
+               [("n", ctypes.c_int64)] + \
+               [(n, ctypes.c_void_p) for n in ("logits", "ce", "pred", "loss", "correct")]
+
+
 ABI_VERSION = 5     # include/eegnet_abi.h EEGNET_ABI_VERSION: the struct layouts these mirrors follow
 
 
@@ -74,6 +81,9 @@ _SIGS = {
     "eegnet_train_step_folds": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64,
                                                ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
+    "eegnet_eval_folds": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int,
+                                         ctypes.c_int64, _vp]),
+    "eegnet_eval_fold_bytes": (ctypes.c_size_t, []),
     "eegnet_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "eegnet_profile_collect": (ctypes.c_int, [ctypes.c_char_p, _vp, _vp, ctypes.c_int, _vp]),
     "eegnet_trace_enable": (ctypes.c_int, [_vp]),
@@ -111,7 +121,8 @@ def load(path: str | None = None):
         if lib.eegnet_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{p} has struct ABI {lib.eegnet_abi_version()}, this binding {ABI_VERSION}: "
                                f"rebuild it")
-        for name, mirror in (("eegnet_dims_bytes", Dims), ("eegnet_fold_bytes", Fold)):
+        for name, mirror in (("eegnet_dims_bytes", Dims), ("eegnet_fold_bytes", Fold),
+                             ("eegnet_eval_fold_bytes", EvalFold)):
             if getattr(lib, name)() != ctypes.sizeof(mirror):
                 raise RuntimeError(f"{p} was built with another {mirror.__name__} layout ({name}() = "
                                    f"{getattr(lib, name)()}, binding {ctypes.sizeof(mirror)}): rebuild it")

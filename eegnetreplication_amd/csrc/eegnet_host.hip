@@ -363,6 +363,7 @@ static void set_attrs_shape() {
     hipFuncSetAttribute((const void*)k_infer_dx<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)k_eval_folds<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 template <int K1>
@@ -1197,6 +1198,49 @@ int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fo
                            mode, &adam, s, fc, nfolds);
 }
 
+int eegnet_eval_folds(const eegnet_dims* dims, int nfolds, const eegnet_eval_fold* folds, int64_t max_n,
+                      int batch, int64_t slot, void* stream) {
+    if (!dims) return fail(EEGNET_EINVAL, "dims is NULL");
+    eegnet_dims d = *dims;
+    d.B = 1;                                          // dims->B is ignored: the table carries every fold's n
+    Geo g;
+    if (int r = make_geo(&d, &g, false)) return r;
+    if (g.wide) return fail(EEGNET_EINVAL, "eegnet_eval_folds: F1*D = %d > 16 is not supported", g.F2);
+    if (int r = make_geo(&d, &g)) return r;
+    if (g.XP != g.T) return fail(EEGNET_EINVAL, "eegnet_eval_folds takes x as [n][C][T] (x_pitch 0 or T)");
+    if (nfolds < 1) return fail(EEGNET_EINVAL, "nfolds must be >= 1 (got %d)", nfolds);
+    if (!folds) return fail(EEGNET_EINVAL, "folds is NULL");
+    if (max_n < 0) return fail(EEGNET_EINVAL, "max_n must be >= 0 (got %lld)", (long long)max_n);
+    if (batch < 1) return fail(EEGNET_EINVAL, "batch must be >= 1 (got %d)", batch);
+    if (max_n > (int64_t)1 << 31) return fail(EEGNET_EINVAL, "max_n must be <= 2^31 (got %lld)", (long long)max_n);
+    if (slot < 0) return fail(EEGNET_EINVAL, "slot must be >= 0");
+    if ((g.ldsI + NCLS) * 4 > LDS_MAX)
+        return fail(EEGNET_EINVAL, "eegnet_eval_folds: dims need %d B of LDS (> %d)", (g.ldsI + NCLS) * 4, LDS_MAX);
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    EvalCall ec;
+    ec.folds = folds;
+    ec.max_n = max_n;
+    ec.total = (long long)nfolds * max_n;
+    ec.slot = slot;
+    ec.batch = batch;
+    if (ec.total > 0) {
+        // a flat grid over the (fold, trial) pairs: at most one workgroup per CU, a contiguous range each
+        const long long G = std::min<long long>(device_cus(), ec.total);
+        ec.chunk = (ec.total + G - 1) / G;
+        const unsigned grid = (unsigned)((ec.total + ec.chunk - 1) / ec.chunk);
+#define LAUNCH_EF(K, CC, TT, FF) hipLaunchKernelGGL((k_eval_folds<K, CC, TT, FF>), dim3(grid), dim3(NTH), \
+                                                    (g.ldsI + NCLS) * 4, s, g, ec)
+        if (g.K1 == 32) EEG_DISPATCH(32, g, LAUNCH_EF); else EEG_DISPATCH(64, g, LAUNCH_EF);
+        LAUNCH_CHECK("k_eval_folds");
+    } else {
+        ec.chunk = 1;
+    }
+    hipLaunchKernelGGL(k_eval_folds_reduce, dim3((unsigned)nfolds), dim3(NTER), 0, s, ec);
+    LAUNCH_CHECK("k_eval_folds_reduce");
+    return 0;
+}
+
 int eegnet_x_stats_width(const eegnet_dims* dims) {
     Geo g;
     if (int r = make_geo(dims, &g, false)) return r;
@@ -1254,6 +1298,7 @@ int eegnet_trace_enable(void* buf) {
 
 size_t eegnet_dims_bytes(void) { return sizeof(eegnet_dims); }
 size_t eegnet_fold_bytes(void) { return sizeof(eegnet_fold); }
+size_t eegnet_eval_fold_bytes(void) { return sizeof(eegnet_eval_fold); }
 int eegnet_abi_version(void) { return EEGNET_ABI_VERSION; }
 
 size_t eegnet_trace_bytes(void) { return (size_t)8 * TR_MAXWG * TR_SLOTS * sizeof(unsigned long long); }

@@ -19,6 +19,8 @@ bit-equality with the same fold run alone).
 
 from __future__ import annotations
 
+import weakref
+
 import torch
 
 from . import ops
@@ -41,6 +43,104 @@ def _refuse_frozen(models):
     if any(getattr(m, "bn_frozen", False) for m in models):
         raise ValueError("FoldBatch does not support models with frozen BatchNorm (EEGNet.freeze_bn): "
                          "fine-tune them with train() / FusedTrainer, or call freeze_bn(False)")
+
+
+class _At:
+    """A raw device address where a table builder expects a tensor (``data_ptr()``)."""
+
+    def __init__(self, p):
+        self.p = p
+
+    def data_ptr(self):
+        return self.p
+
+
+_eval_states: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()    # models[0] -> evaluate_folds state
+
+
+def evaluate_folds(models, sets, batch_size: int = 64, *, out=None):
+    """Validate every model on its own held-out set with one fold-indexed call (eegnet_eval_folds):
+    the eval-mode forward (running statistics, no dropout, whatever mode the modules are in), the
+    per-trial cross-entropy and the argmax of all folds in one launch, and per fold the reference's
+    validation loss -- the mean over the batches of ``batch_size`` consecutive trials (the last one
+    short) of each batch's mean CE, model.py:156-172 -- and the number of correct trials.
+
+    ``sets[k] = (X_k [n_k, C, T] float32, y_k [n_k] int64)``: contiguous device tensors, sizes may
+    differ, folds may share a set.  Returns ``(loss float64 [k], correct int64 [k])`` device tensors;
+    nothing is synchronised and no torch kernel runs.  ``out``: a ``(loss, correct)`` pair of
+    contiguous [k] tensors (float64, int64) to receive the results -- rows of two larger buffers, say
+    -- instead of the call's own pair, which the next call on the same models and sets overwrites.
+
+    The fold table, the per-trial scratch and the outputs are built once per (models, sets) identity
+    and reused: training updates parameters and BN buffers in place, so the pointers stay valid.  They
+    are rebuilt when a model's flat parameter / BN buffer or a set tensor is another object."""
+    K = len(models)
+    if K < 1 or len(sets) != K:
+        raise ValueError("need at least one model and one (X, y) per model")
+    if out is not None:
+        lo, co = out
+        if (tuple(lo.shape) != (K,) or tuple(co.shape) != (K,) or lo.dtype != torch.float64
+                or co.dtype != torch.int64 or not lo.is_contiguous() or not co.is_contiguous()
+                or lo.device != co.device):
+            raise ValueError(f"out must be (float64 [{K}], int64 [{K}]) contiguous tensors on one device")
+        # a row of a larger buffer is that buffer's table at another slot: no new table per row
+        bases = (lo.untyped_storage().data_ptr(), co.untyped_storage().data_ptr())
+        slot = lo.storage_offset()
+        if co.storage_offset() != slot:
+            bases, slot = (lo.data_ptr(), co.data_ptr()), 0
+    else:
+        bases, slot = None, 0
+    # every raw device pointer the table holds, and the identity of what it was taken from (the state
+    # keeps the set tensors alive, so an id cannot come back as another tensor); one flat-layout check
+    # per model (flat_views), which re-flattens a model whose parameters were re-created
+    views = [m.flat_views() for m in models]
+    key = (bases, tuple((id(m), v[0].data_ptr(), v[1].data_ptr(), id(X), X.data_ptr(), X.shape[0], id(y),
+                         y.data_ptr()) for m, v, (X, y) in zip(models, views, sets)))
+    st = _eval_states.get(models[0])
+    if st is None or st["key"] != key:
+        shape = models[0].shape
+
+        def geom(s):                  # what the eval forward reads of a Shape (not p, not the momentum)
+            return (s.C, s.T, s.F1, s.D, s.K1, s.eps)
+        if any(geom(m.shape) != geom(shape) for m in models) or shape.F2 > 16:
+            raise ValueError("evaluate_folds needs one common EEGNet shape with F1*D <= 16 for every model: "
+                             "evaluate other models one at a time (model.eval(); model(X), or evaluate_model())")
+        dev = views[0][0].device
+        if dev.type != "cuda":
+            raise RuntimeError("evaluate_folds runs on a HIP device only")
+        for X, y in sets:
+            if (X.device != dev or y.device != dev or X.dtype != torch.float32 or y.dtype != torch.int64
+                    or X.dim() != 3 or tuple(X.shape[1:]) != (shape.C, shape.T) or tuple(y.shape) != (X.shape[0],)):
+                raise ValueError(f"every set must be (X [n, {shape.C}, {shape.T}] float32, y [n] int64) on {dev}")
+            if not X.is_contiguous() or not y.is_contiguous():
+                raise ValueError("evaluate_folds takes contiguous X and y (call .contiguous() once, outside "
+                                 "the loop)")
+            if shape.T % 4 == 0 and X.data_ptr() % 16:
+                raise ValueError("X must be 16-byte aligned when T % 4 == 0")
+        if out is not None and lo.device != dev:
+            raise ValueError(f"out must be on {dev}")
+        ns = [int(X.shape[0]) for X, _ in sets]
+        ce = torch.empty(max(sum(ns), 1), dtype=torch.float32, device=dev)
+        pred = torch.empty(max(sum(ns), 1), dtype=torch.int32, device=dev)
+        st = {"key": key, "shape": shape, "src": list(sets), "ce": ce, "pred": pred, "max_n": max(ns)}
+        if out is None:
+            st["loss"] = torch.zeros(K, dtype=torch.float64, device=dev)
+            st["correct"] = torch.zeros(K, dtype=torch.int64, device=dev)
+            lp, cp = st["loss"].data_ptr(), st["correct"].data_ptr()
+        else:
+            st["hold"] = (lo.untyped_storage(), co.untyped_storage())
+            lp, cp = bases
+        ents, o = [], 0
+        for k, (v, (X, y)) in enumerate(zip(views, sets)):
+            ents.append(dict(params=v[0], bn_buffers=v[1], x=X, labels=y, n=ns[k],
+                             logits=None, ce=_At(ce.data_ptr() + 4 * o), pred=_At(pred.data_ptr() + 4 * o),
+                             loss=_At(lp + 8 * k), correct=_At(cp + 8 * k)))
+            o += ns[k]
+        st["table"] = ops.eval_fold_table(ents, dev)
+        _eval_states[models[0]] = st
+    shape = st["shape"]
+    ops.eval_folds(shape, st["table"], K, st["max_n"], batch=int(batch_size), slot=slot)
+    return (st["loss"], st["correct"]) if out is None else (lo, co)
 
 
 class FoldBatch:
@@ -87,6 +187,11 @@ class FoldBatch:
 
     def __len__(self):
         return len(self.models)
+
+    def validate(self, sets, batch_size: int = 64):
+        """``evaluate_folds`` on this batch's models: per fold the validation loss (float64) and the
+        number of correct trials (int64) on ``sets[k] = (X_k, y_k)``, as device tensors, unsynchronised."""
+        return evaluate_folds(self.models, sets, batch_size)
 
     def invalidate_x(self):
         """Recompute every fold's padded x copy and per-trial BN1 table from its X at the next epoch

@@ -374,3 +374,28 @@ def train_step_folds(shape: Shape, B: int, table: torch.Tensor, nfolds: int, row
         ctypes.byref(d), ctypes.c_int(nfolds), _ptr(table), ctypes.c_int64(row0), ctypes.c_int64(slot),
         ctypes.c_uint64(offset), ctypes.c_float(lr), ctypes.c_float(betas[0]), ctypes.c_float(betas[1]),
         ctypes.c_float(eps), _stream()), "eegnet_train_step_folds")
+
+
+def eval_fold_table(entries, device) -> torch.Tensor:
+    """Device array of ``eegnet_eval_fold`` entries (a uint8 tensor holding the packed structs).
+    ``entries``: dicts with the eegnet_eval_fold pointer fields as tensors (or None) and ``n`` as an
+    int."""
+    arr = (_lib.EvalFold * len(entries))()
+    for i, e in enumerate(entries):
+        for name, _ in _lib.EvalFold._fields_:
+            if name == "n":
+                continue
+            t = e.get(name)
+            setattr(arr[i], name, 0 if t is None else t.data_ptr())
+        arr[i].n = int(e["n"])
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def eval_folds(shape: Shape, table: torch.Tensor, nfolds: int, max_n: int, batch: int = 64, slot: int = 0):
+    """eegnet_eval_folds: the eval forward, per-trial cross-entropy and argmax of ``nfolds`` models on
+    their own held-out sets in one launch, then each fold's validation loss (the mean of the per-batch CE
+    means over batches of ``batch`` trials, float64) and correct count into loss[slot] / correct[slot].
+    ``table`` from eval_fold_table(); ``max_n`` the largest ``n`` in it.  No host synchronisation."""
+    _lib.check(_lib.load().eegnet_eval_folds(
+        ctypes.byref(shape.dims(1)), ctypes.c_int(nfolds), _ptr(table), ctypes.c_int64(max_n),
+        ctypes.c_int(batch), ctypes.c_int64(slot), _stream()), "eegnet_eval_folds")

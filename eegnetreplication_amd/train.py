@@ -69,14 +69,14 @@ def _run_fold(X, y, tr_ids, va_ids, te, p, epochs, seed, device):
 
 def _run_folds(specs, epochs, device):
     """Several independent units trained together by FoldBatch:
-    per-fold streams, one captured hipGraph per fold epoch, no host sync until the end.  Each
-    spec is _run_fold's arguments (X, y, tr_ids, va_ids, te, p, seed).  Per fold and epoch, as in
+    fold-indexed launches, one captured hipGraph per epoch, one fold-indexed validation call per epoch
+    (evaluate_folds), no host sync until the end.  Each spec is _run_fold's arguments (X, y, tr_ids,
+    va_ids, te, p, seed).  Per fold and epoch, as in
     train() (model.py:101-189): the train loss is the mean of the batch losses, the validation
     loss the mean of per-batch CE means over batches of 64, the validation accuracy over all
     validation trials; the returned state is the final weights (the reference's aliasing "best",
     SURVEY F4).  Returns one result dict per spec, like _run_fold."""
-    import torch.nn.functional as F
-    from .folds import FoldBatch
+    from .folds import FoldBatch, evaluate_folds
     models, seeds, train_sets, val_sets, test_sets, gens = [], [], [], [], [], []
     for X, y, tr_ids, va_ids, te, p, seed in specs:
         torch.manual_seed(seed)
@@ -90,49 +90,30 @@ def _run_folds(specs, epochs, device):
         val_sets.append((dev(X[va_ids], torch.float32), dev(y[va_ids], torch.int64)))
         test_sets.append((dev(te[0], torch.float32), dev(te[1], torch.int64)))
     fb = FoldBatch(models, seeds, graphs=True)
-    val_loss = [[] for _ in specs]
-    val_acc = [[] for _ in specs]
-    # validation in groups of folds with the same validation size: one eval launch per fold, then
-    # one set of loss / accuracy reductions per group instead of per fold
-    groups = {}
-    for k, (_, yv) in enumerate(val_sets):
-        groups.setdefault(len(yv), []).append(k)
-    vgroups = []
-    for nv, ks in groups.items():
-        nb = (nv + BATCH_SIZE - 1) // BATCH_SIZE
-        seg = torch.arange(nv, device=device) // BATCH_SIZE
-        vgroups.append((ks, nb, seg, torch.bincount(seg, minlength=nb).double(),
-                        torch.stack([val_sets[k][1] for k in ks])))
+    K = len(specs)
+    # validation: one fold-indexed call per epoch (evaluate_folds: every fold's eval forward, per-trial CE
+    # and argmax in one launch, the per-fold loss and correct count in a second) on the current stream
+    # behind the epoch's training, into row e of two [epochs, K] device buffers; no torch kernel and no
+    # module mode change in between
+    vloss = torch.zeros((epochs, K), dtype=torch.float64, device=device)
+    vcorr = torch.zeros((epochs, K), dtype=torch.int64, device=device)
     for e in range(1, epochs + 1):
         fb.epoch(train_sets, BATCH_SIZE, gens)
-        with torch.no_grad():
-            logits = []
-            for m, (Xv, _) in zip(models, val_sets):
-                m.eval()
-                logits.append(m(Xv))                # eval BN: batch-size independent
-                m.train()
-            for ks, nb, seg, cnt, Y in vgroups:
-                L = torch.stack([logits[k] for k in ks])                      # [G, nv, classes]
-                ce = F.cross_entropy(L.flatten(0, 1), Y.flatten(), reduction="none").view(Y.shape)
-                means = torch.zeros((len(ks), nb), dtype=torch.float64, device=ce.device).index_add_(
-                    1, seg, ce.double()) / cnt
-                vl = means.mean(1)
-                va = (L.argmax(2) == Y).sum(1)
-                for j, k in enumerate(ks):
-                    val_loss[k].append(vl[j])
-                    val_acc[k].append(va[j])
+        evaluate_folds(models, val_sets, BATCH_SIZE, out=(vloss[e - 1], vcorr[e - 1]))
         if e == 1 or e % 50 == 0 or e == epochs:
             logger.info(f"Epoch: {e}/{epochs} ({len(specs)} folds batched)")
+    _, tcorr = evaluate_folds(models, test_sets, BATCH_SIZE)
+    # the one device-to-host copy of the fold batch's metrics (counts are exact in float64)
+    host = torch.cat([vloss.flatten(), vcorr.flatten().double(), tcorr.double()]).cpu().numpy()
+    vl = host[:epochs * K].reshape(epochs, K)
+    vc = host[epochs * K:2 * epochs * K].reshape(epochs, K)
+    tc = host[2 * epochs * K:]
     out = []
     for k, m in enumerate(models):
         m.eval()
-        Xt, yt = test_sets[k]
-        with torch.no_grad():
-            correct = int((m(Xt).argmax(1) == yt).sum().item())
-        vl = torch.stack(val_loss[k]).cpu().numpy()
-        va = 100.0 * torch.stack(val_acc[k]).cpu().numpy() / len(val_sets[k][1])
-        out.append({"test_acc": 100 * correct / len(yt), "val_acc": float(va.max()),
-                    "val_loss": float(vl.min()),
+        va = 100.0 * vc[:, k] / len(val_sets[k][1])
+        out.append({"test_acc": 100 * int(tc[k]) / len(test_sets[k][1]), "val_acc": float(va.max()),
+                    "val_loss": float(vl[:, k].min()),
                     "state": {n: v.detach().cpu() for n, v in m.state_dict().items()}})
     return out
 

@@ -8,6 +8,7 @@
  *   one hot-loop iteration    src/eegnet_repl/model.py:136-148 -> eegnet_train_step
  *   saliency / x.grad in .eval() (plain autograd on the nn.Module) -> eegnet_input_grad_eval
  *   the hot loop with bn.eval() on the three BatchNorm2d (fine-tuning) -> eegnet_frozen_step
+ *   the per-epoch validation loop src/eegnet_repl/model.py:151-172, many folds at once -> eegnet_eval_folds
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer (hipMalloc / torch CUDA tensor) unless noted.  The library never
@@ -236,6 +237,41 @@ int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fo
                             int64_t slot, uint64_t offset, float lr, float beta1, float beta2, float eps,
                             void* stream);
 
+/* One model (fold) of a fold-indexed validation call.  Every pointer is a device pointer; an array of
+ * these lives in DEVICE memory.  Nothing in it is written except through logits, ce, pred, loss and
+ * correct. */
+typedef struct eegnet_eval_fold {
+    const float* params;       /* flat parameters                                  */
+    const float* bn_buffers;   /* rm1 rv1 rm2 rv2 rm3 rv3 (read only)              */
+    const float* x;            /* [n, C, T] contiguous; folds may share one        */
+    const int64_t* labels;     /* [n] in [0,4); NULL: logits / pred only           */
+    int64_t n;                 /* trials of this fold (0: nothing read, loss 0, correct 0) */
+    float* logits;             /* [n,4] or NULL                                    */
+    float* ce;                 /* [n] per-trial CE; required when labels != NULL   */
+    int32_t* pred;             /* [n] argmax; required when labels != NULL         */
+    double* loss;              /* loss[slot] (needs labels) or NULL                */
+    int64_t* correct;          /* correct[slot] (needs labels) or NULL             */
+} eegnet_eval_fold;
+
+/* Validation of `nfolds` independent models, each on its own held-out set, as model.py:151-172 computes
+ * it after every epoch: the eval-mode forward of eegnet_forward_eval per trial (the same per-trial code:
+ * a fold's logits are bit-identical to that call on the fold alone), the trial's cross-entropy
+ * ce[i] = logsumexp(logits[i]) - logits[i][labels[i]] and its prediction pred[i] (argmax, the lowest
+ * index on a tie) in one launch over every fold's trials; then, one workgroup per fold,
+ *     loss[slot]    = (1/nb) sum_j mean_{i in batch j} ce[i],  nb = ceil(n / batch)
+ *                     (batches of `batch` consecutive trials, the last one short; fp64, index order:
+ *                     running_val_loss / len(val_loader))
+ *     correct[slot] = #{i : pred[i] == labels[i]}.
+ * `folds` is a DEVICE array the host never reads; max_n, 0 <= max_n <= 2^31, must be the largest n in it
+ * (it sizes the grid: trials at or beyond max_n would not be evaluated).  dims->B is ignored.
+ * batch >= 1; batch >= n makes the loss a plain mean.  Each output is written only when its pointer is non-NULL (ce, loss and correct
+ * also need labels; a fold with n = 0 reads none of its pointers and reports loss 0, correct 0 with or
+ * without them).  No atomics: the same inputs give the same bits.  F1*D <= 16 only, x_pitch 0 or T, x
+ * 16-byte aligned when T % 4 == 0; the shapes eegnet_train_step_folds takes.  No host synchronisation:
+ * capturable in a hipGraph.  The validation needs no GPU. */
+int eegnet_eval_folds(const eegnet_dims* dims, int nfolds, const eegnet_eval_fold* folds,
+                      int64_t max_n, int batch, int64_t slot, void* stream);
+
 /* Per-trial BatchNorm-1 statistics of x that do not depend on the parameters: for each of the n
  * trials x[i] ([C][T] rows at dims->x_pitch), the lag sums of its zero-padded rows summed over the
  * channels G0[d] (d < K1), the window-0 sample sum, and the head / tail products and sums of the
@@ -280,11 +316,12 @@ int eegnet_x_pitch(const eegnet_dims* dims);
  * differing geometry fields are then in eegnet_last_error()), < 0 on invalid dims.  No GPU needed. */
 int eegnet_wide_spec(const eegnet_dims* dims);
 
-/* sizeof(eegnet_dims) and sizeof(eegnet_fold) as this library was compiled: a binding checks its
- * struct mirrors against them at load (a stale library with another fold layout would read every
- * fold after the first from the wrong offsets). */
+/* sizeof(eegnet_dims), sizeof(eegnet_fold) and sizeof(eegnet_eval_fold) as this library was compiled: a
+ * binding checks its struct mirrors against them at load (a stale library with another fold layout
+ * would read every fold after the first from the wrong offsets). */
 size_t eegnet_dims_bytes(void);
 size_t eegnet_fold_bytes(void);
+size_t eegnet_eval_fold_bytes(void);
 
 /* The struct layouts above are versioned: EEGNET_ABI_VERSION changes whenever a field of eegnet_dims
  * or eegnet_fold moves (a reordering keeps the size, so eegnet_fold_bytes alone cannot catch it).
