@@ -90,6 +90,7 @@ _SIGS = {
     "eegnet_trace_bytes": (ctypes.c_size_t, []),
     "eegnet_dims_bytes": (ctypes.c_size_t, []),
     "eegnet_wide_spec": (ctypes.c_int, [ctypes.POINTER(Dims)]),
+    "eegnet_launch_grids": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "eegnet_x_pitch": (ctypes.c_int, [ctypes.POINTER(Dims)]),
     "eegnet_x_stats_width": (ctypes.c_int, [ctypes.POINTER(Dims)]),
     "eegnet_x_stats": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int64, _vp, _vp, _vp]),

@@ -441,6 +441,27 @@ static bool same_shape_w5(const Geo& g) {
         else hipLaunchKernelGGL(KG, grid_, blk_, lds_, __VA_ARGS__);                              \
     } while (0)
 
+// Workgroup counts of the passes that choose among the Geo grids (build options): the F2 <= 16
+// launches of run_backward use them and eegnet_launch_grids reports them.  For F2 > 16 they name the
+// Geo fields run_forward_wide / run_backward_wide launch with (gridW2, grid); those launches do not
+// call them.  grid_wpass_b restates the grid expression on k_wpass_b's launch line in
+// run_forward_wide (the cfg5 instantiation runs two workgroups per CU) for the query alone: keep the
+// two alike.
+static int grid_wpass_b(const Geo& g, bool sp) { return sp ? std::min(2 * g.gridS, g.B * g.NOC) : g.gridS; }
+static int grid_pass_c(const Geo& g) { return g.wide ? g.gridW2 : use_b2_narrow(g) ? g.gridB2 : g.grid; }
+static int grid_pass_d(const Geo& g) {
+    return g.wide ? g.grid : use_b2_narrow(g) ? g.gridB2 : EEGNET_D1 ? g.grid : g.gridS;   // (k_pass_dr: gridS)
+}
+// Trial streams of passes C / D: k_pass_c and k_pass_d (-DEEGNET_D1=1) give each of a workgroup's nwC /
+// nwD waves its own trials (wave i of workgroup r: rows r nw + i, + grid nw, ...), every other kernel
+// runs a workgroup's trials one after the other
+static int streams_pass_c(const Geo& g) {
+    return grid_pass_c(g) * ((g.wide || use_b2_narrow(g)) ? 1 : g.nwC);
+}
+static int streams_pass_d(const Geo& g) {
+    return grid_pass_d(g) * ((g.wide || use_b2_narrow(g) || !EEGNET_D1) ? 1 : g.nwD);
+}
+
 // F2 > 16: passes A, B (no reduction), B2 (BN3 statistics)
 template <int K1>
 static int run_forward_wide(const Geo& g, const WsLayout& L, char* ws, const float* params, float* bn,
@@ -553,29 +574,29 @@ static int run_backward(const Geo& g, const WsLayout& L, char* ws, float* params
         fe.params = params; fe.adam_m = adam->adam_m; fe.adam_v = adam->adam_v; fe.step = adam->step;
         fe.lr = adam->lr; fe.b1 = adam->b1; fe.b2 = adam->b2; fe.eps = adam->eps;
     }
-#define LAUNCH_CB(K, CC, TT, FF) if (fc.folds) hipLaunchKernelGGL((k_pass_c<K, CC, TT, FF, true>), dim3(g.grid, nf), dim3(64 * g.nwC), g.ldsC * 4, s, \
+#define LAUNCH_CB(K, CC, TT, FF) if (fc.folds) hipLaunchKernelGGL((k_pass_c<K, CC, TT, FF, true>), dim3(grid_pass_c(g), nf), dim3(64 * g.nwC), g.ldsC * 4, s, \
                        g, params, coef, (const float*)(ws + L.r3), m3, dlogits, labels, logits, \
                        (float*)(ws + L.dl), (float*)(ws + L.partC), c_mode, fcC, fc); \
-    else hipLaunchKernelGGL((k_pass_c<K, CC, TT, FF>), dim3(g.grid, nf), dim3(64 * g.nwC), g.ldsC * 4, s, \
+    else hipLaunchKernelGGL((k_pass_c<K, CC, TT, FF>), dim3(grid_pass_c(g), nf), dim3(64 * g.nwC), g.ldsC * 4, s, \
                        g, params, coef, (const float*)(ws + L.r3), m3, dlogits, labels, logits, \
                        (float*)(ws + L.dl), (float*)(ws + L.partC), c_mode, fcC, fc)
     if (use_b2_narrow(g)) {
         if (only >= 0) return fail(EEGNET_EINVAL, "staged steps do not support EEGNET_B2=1");
         { PROF(KID_C);
-          if (fc.folds) hipLaunchKernelGGL((k_wpass_c<256, true>), dim3(g.gridB2, nf), dim3(256), g.ldsWC * 4, s, g,
+          if (fc.folds) hipLaunchKernelGGL((k_wpass_c<256, true>), dim3(grid_pass_c(g), nf), dim3(256), g.ldsWC * 4, s, g,
                                            params, coef, (const float*)(ws + L.r3), m3, dlogits, labels, logits,
                                            (float*)(ws + L.dl), (float*)(ws + L.partC), c_mode, fcC, fc);
-          else hipLaunchKernelGGL((k_wpass_c<256>), dim3(g.gridB2), dim3(256), g.ldsWC * 4, s, g, params, coef,
+          else hipLaunchKernelGGL((k_wpass_c<256>), dim3(grid_pass_c(g)), dim3(256), g.ldsWC * 4, s, g, params, coef,
                                   (const float*)(ws + L.r3), m3, dlogits, labels, logits, (float*)(ws + L.dl),
                                   (float*)(ws + L.partC), c_mode, fcC, fc);
         } LAUNCH_CHECK("k_wpass_c<256>");
         { PROF(KID_D);
-          if (fc.folds) hipLaunchKernelGGL((k_wpass_d<256, true>), dim3(g.gridB2, nf), dim3(256), g.ldsWD * 4, s, g,
+          if (fc.folds) hipLaunchKernelGGL((k_wpass_d<256, true>), dim3(grid_pass_d(g), nf), dim3(256), g.ldsWD * 4, s, g,
                                            params, coef, (const float*)(ws + L.d2), (const float*)(ws + L.E1),
                                            (const float*)(ws + L.E2), (const float*)(ws + L.q3),
                                            (const float*)(ws + L.r3), m2, m3, dl, (float*)(ws + L.dp2),
                                            (float*)(ws + L.partD), fd, fc);
-          else hipLaunchKernelGGL((k_wpass_d<256>), dim3(g.gridB2), dim3(256), g.ldsWD * 4, s, g, params, coef,
+          else hipLaunchKernelGGL((k_wpass_d<256>), dim3(grid_pass_d(g)), dim3(256), g.ldsWD * 4, s, g, params, coef,
                                   (const float*)(ws + L.d2), (const float*)(ws + L.E1), (const float*)(ws + L.E2),
                                   (const float*)(ws + L.q3), (const float*)(ws + L.r3), m2, m3, dl,
                                   (float*)(ws + L.dp2), (float*)(ws + L.partD), fd, fc);
@@ -583,32 +604,32 @@ static int run_backward(const Geo& g, const WsLayout& L, char* ws, float* params
     } else {
     if (only < 0 || only == 2) { { PROF(KID_C); EEG_DISPATCH(K1, g, LAUNCH_CB);
     } LAUNCH_CHECK("k_pass_c(bwd)"); }
-#define LAUNCH_DR(K, CC, TT, FF) if (fc.folds) hipLaunchKernelGGL((k_pass_dr<K, CC, TT, FF, true, false>), dim3(g.gridS, nf), dim3(NTB), g.ldsD * 4, s, \
+#define LAUNCH_DR(K, CC, TT, FF) if (fc.folds) hipLaunchKernelGGL((k_pass_dr<K, CC, TT, FF, true, false>), dim3(grid_pass_d(g), nf), dim3(NTB), g.ldsD * 4, s, \
                        g, params, coef, (const float*)(ws + L.d2), (const float*)(ws + L.E1), \
                        (const float*)(ws + L.E2), (const float*)(ws + L.q3), (const float*)(ws + L.r3), \
                        m2, m3, dl, (float*)(ws + L.dp2), \
                        (float*)(ws + L.partD), fd, fc); \
-    else if (m2 || m3) hipLaunchKernelGGL((k_pass_dr<K, CC, TT, FF>), dim3(g.gridS, nf), dim3(NTB), g.ldsD * 4, s, \
+    else if (m2 || m3) hipLaunchKernelGGL((k_pass_dr<K, CC, TT, FF>), dim3(grid_pass_d(g), nf), dim3(NTB), g.ldsD * 4, s, \
                        g, params, coef, (const float*)(ws + L.d2), (const float*)(ws + L.E1), \
                        (const float*)(ws + L.E2), (const float*)(ws + L.q3), (const float*)(ws + L.r3), \
                        m2, m3, dl, (float*)(ws + L.dp2), \
                        (float*)(ws + L.partD), fd, fc); \
-    else hipLaunchKernelGGL((k_pass_dr<K, CC, TT, FF, false, false>), dim3(g.gridS, nf), dim3(NTB), g.ldsD * 4, s, \
+    else hipLaunchKernelGGL((k_pass_dr<K, CC, TT, FF, false, false>), dim3(grid_pass_d(g), nf), dim3(NTB), g.ldsD * 4, s, \
                        g, params, coef, (const float*)(ws + L.d2), (const float*)(ws + L.E1), \
                        (const float*)(ws + L.E2), (const float*)(ws + L.q3), (const float*)(ws + L.r3), \
                        m2, m3, dl, (float*)(ws + L.dp2), \
                        (float*)(ws + L.partD), fd, fc)
-#define LAUNCH_D(K, CC, TT, FF) if (fc.folds) hipLaunchKernelGGL((k_pass_d<K, CC, TT, FF, true, false>), dim3(g.grid, nf), dim3(64 * g.nwD), g.ldsD * 4, s, \
+#define LAUNCH_D(K, CC, TT, FF) if (fc.folds) hipLaunchKernelGGL((k_pass_d<K, CC, TT, FF, true, false>), dim3(grid_pass_d(g), nf), dim3(64 * g.nwD), g.ldsD * 4, s, \
                        g, params, coef, (const float*)(ws + L.d2), (const float*)(ws + L.E1), \
                        (const float*)(ws + L.E2), (const float*)(ws + L.q3), (const float*)(ws + L.r3), \
                        m2, m3, dl, (float*)(ws + L.dp2), \
                        (float*)(ws + L.partD), fd, fc); \
-    else if (m2 || m3) hipLaunchKernelGGL((k_pass_d<K, CC, TT, FF>), dim3(g.grid, nf), dim3(64 * g.nwD), g.ldsD * 4, s, \
+    else if (m2 || m3) hipLaunchKernelGGL((k_pass_d<K, CC, TT, FF>), dim3(grid_pass_d(g), nf), dim3(64 * g.nwD), g.ldsD * 4, s, \
                        g, params, coef, (const float*)(ws + L.d2), (const float*)(ws + L.E1), \
                        (const float*)(ws + L.E2), (const float*)(ws + L.q3), (const float*)(ws + L.r3), \
                        m2, m3, dl, (float*)(ws + L.dp2), \
                        (float*)(ws + L.partD), fd, fc); \
-    else hipLaunchKernelGGL((k_pass_d<K, CC, TT, FF, false, false>), dim3(g.grid, nf), dim3(64 * g.nwD), g.ldsD * 4, s, \
+    else hipLaunchKernelGGL((k_pass_d<K, CC, TT, FF, false, false>), dim3(grid_pass_d(g), nf), dim3(64 * g.nwD), g.ldsD * 4, s, \
                        g, params, coef, (const float*)(ws + L.d2), (const float*)(ws + L.E1), \
                        (const float*)(ws + L.E2), (const float*)(ws + L.q3), (const float*)(ws + L.r3), \
                        m2, m3, dl, (float*)(ws + L.dp2), \
@@ -701,6 +722,16 @@ static bool same_geo_bf16(GeoI a, GeoI b) {
     return memcmp(&a, &b, sizeof(GeoI)) == 0;
 }
 
+// The train step of the F2 > 16 path with 64 temporal taps (k_wpass_a<64> / k_wpass_e<64>) is refused:
+// at EEGNet-8,4 on 5 x 72 (B = 513) it ended in a GPU memory fault whose cause is not known, and no
+// test has seen it produce a result.  The eval forward of these dims (k_winfer<64>) is tested and stays.
+static int check_wide_train(const Geo& g, const char* what) {
+    if (g.wide && g.K1 == 64)
+        return fail(EEGNET_EINVAL, "%s: training with F1*D = %d > 16 and K1 = 64 is not supported "
+                    "(K1 = 32, or F1*D <= 16; the eval forward takes these dims)", what, g.F2);
+    return 0;
+}
+
 static int check_ptrs(const void* a, const char* na, const void* b = (const void*)1, const char* nb = "") {
     if (!a) return fail(EEGNET_EINVAL, "%s is NULL", na);
     if (!b) return fail(EEGNET_EINVAL, "%s is NULL", nb);
@@ -751,6 +782,7 @@ int eegnet_forward_train(const eegnet_dims* dims, const float* params, float* bn
                          int64_t* num_batches_tracked) {
     Geo g;
     if (int r = make_geo(dims, &g)) return r;
+    if (int r = check_wide_train(g, "eegnet_forward_train")) return r;
     if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
     if (int r = check_ptrs(x, "x", logits, "logits")) return r;
     if (int r = check_ptrs(ws, "ws")) return r;
@@ -790,6 +822,7 @@ int eegnet_backward(const eegnet_dims* dims, const float* params, const float* x
                     void* ws, void* stream, int flags) {
     Geo g;
     if (int r = make_geo(dims, &g)) return r;
+    if (int r = check_wide_train(g, "eegnet_backward")) return r;
     g.noclamp = (flags & EEGNET_NO_CLAMP) ? 1 : 0;
     if (int r = check_ptrs(params, "params", x, "x")) return r;
     if (int r = check_ptrs(grads, "grads", ws, "ws")) return r;
@@ -916,6 +949,7 @@ int eegnet_train_step(const eegnet_dims* dims, float* params, float* bn_buffers,
                       int64_t* num_batches_tracked) {
     Geo g;
     if (int r = make_geo(dims, &g)) return r;
+    if (int r = check_wide_train(g, "eegnet_train_step")) return r;
     if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
     if (int r = check_ptrs(x, "x", labels, "labels")) return r;
     if (int r = check_ptrs(grads, "grads", ws, "ws")) return r;
@@ -1149,6 +1183,22 @@ static void fold_tpw(int* s, int* c, int* b2) {
     *s = EEGNET_FOLD_TPW_S; *c = EEGNET_FOLD_TPW_C; *b2 = EEGNET_FOLD_TPW_B2;
 }
 
+// The per-fold grids of a fold-indexed launch.  The folds share the chip: each workgroup runs several
+// trials of its fold (its prologue and the reduction tail are per workgroup).  The per-fold grid is a
+// function of B alone -- never of nfolds -- so a fold's trial -> workgroup split, and with it every
+// partial sum and every bit of its result, does not depend on how many folds share the launch
+// (fold-batch width, sharding over ranks).  Capped at the non-fold grids the workspace's partial rows
+// are sized for.
+static void fold_grids(Geo* g) {
+    int tpwS, tpwC, tpwB2;
+    fold_tpw(&tpwS, &tpwC, &tpwB2);
+    g->gridA = std::max(1, std::min(g->gridS, (g->B + EEGNET_FOLD_TPW_A - 1) / EEGNET_FOLD_TPW_A));
+    g->gridE = std::max(1, std::min(g->gridS, (g->B + EEGNET_FOLD_TPW_E - 1) / EEGNET_FOLD_TPW_E));
+    g->gridS = std::max(1, std::min(g->gridS, (g->B + tpwS - 1) / tpwS));
+    g->grid = std::max(1, std::min(g->grid, (g->B + tpwC - 1) / tpwC));
+    g->gridB2 = std::max(1, std::min(g->gridB2, (g->B + tpwB2 - 1) / tpwB2));
+}
+
 extern "C" {
 
 int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
@@ -1164,18 +1214,7 @@ int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fo
     set_key(&g, 0, offset);                           // the keep threshold (keys come per fold)
     ensure_attrs();
     const WsLayout L = make_layout(g);
-    // the folds share the chip: each workgroup runs several trials of its fold (its prologue and the
-    // reduction tail are per workgroup).  The per-fold grid is a function of B alone -- never of
-    // nfolds -- so a fold's trial -> workgroup split, and with it every partial sum and every bit of
-    // its result, does not depend on how many folds share the launch (fold-batch width, sharding
-    // over ranks).  Capped at the non-fold grids the workspace's partial rows are sized for.
-    int tpwS, tpwC, tpwB2;
-    fold_tpw(&tpwS, &tpwC, &tpwB2);
-    g.gridA = std::max(1, std::min(g.gridS, (g.B + EEGNET_FOLD_TPW_A - 1) / EEGNET_FOLD_TPW_A));
-    g.gridE = std::max(1, std::min(g.gridS, (g.B + EEGNET_FOLD_TPW_E - 1) / EEGNET_FOLD_TPW_E));
-    g.gridS = std::max(1, std::min(g.gridS, (g.B + tpwS - 1) / tpwS));
-    g.grid = std::max(1, std::min(g.grid, (g.B + tpwC - 1) / tpwC));
-    g.gridB2 = std::max(1, std::min(g.gridB2, (g.B + tpwB2 - 1) / tpwB2));
+    fold_grids(&g);
     FoldCall fc;
     memset(&fc, 0, sizeof(fc));
     fc.folds = folds;
@@ -1238,6 +1277,25 @@ int eegnet_eval_folds(const eegnet_dims* dims, int nfolds, const eegnet_eval_fol
     }
     hipLaunchKernelGGL(k_eval_folds_reduce, dim3((unsigned)nfolds), dim3(NTER), 0, s, ec);
     LAUNCH_CHECK("k_eval_folds_reduce");
+    return 0;
+}
+
+int eegnet_launch_grids(const eegnet_dims* dims, int fold_launch, int out[6]) {
+    Geo g;
+    if (int r = make_geo(dims, &g)) return r;
+    if (!out) return fail(EEGNET_EINVAL, "out is NULL");
+    if (fold_launch) {
+        if (g.wide) return fail(EEGNET_EINVAL, "eegnet_train_step_folds: F1*D = %d > 16 is not supported", g.F2);
+        fold_grids(&g);
+    }
+    // the wide streaming passes run NOC chunk workgroups per trial range (wide_unit)
+    const int noc = g.wide ? g.NOC : 1;
+    out[0] = g.gridA / noc;
+    out[1] = (g.wide ? grid_wpass_b(g, g.K1 == 32 && same_shape_w5(g)) : g.gridS) / noc;
+    out[2] = streams_pass_c(g);
+    out[3] = streams_pass_d(g);
+    out[4] = g.gridE / noc;
+    out[5] = fold_launch ? 0 : g.grid;      // (eegnet_eval_folds splits by its fold table, not by dims)
     return 0;
 }
 

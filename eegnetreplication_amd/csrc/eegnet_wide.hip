@@ -478,7 +478,9 @@ __global__ __launch_bounds__(NTW) void k_wpass_b(Geo gin, const float* __restric
                             e1 += dz;
                             e2 = fmaf(dz, xh, e2);
                         }
-                        d2o[h] = pe * 0.25f * keep_mul(g, mask2, dk0, (unsigned)(rb + q));
+                        // T % 8 != 0: the last octet's second sample q = T1 is never stored, and its
+                        // keep factor is not read either (an injected mask ends with the row)
+                        d2o[h] = q < T1 ? pe * 0.25f * keep_mul(g, mask2, dk0, (unsigned)(rb + q)) : 0.f;
                         e1o[h] = e1;
                         e2o[h] = e2;
                     }

@@ -100,6 +100,21 @@ class Shape:
                 ("block_2.2.running_mean", F2), ("block_2.2.running_var", F2)]
 
 
+PASSES = ("A", "B", "C", "D", "E", "eval")
+
+
+def launch_grids(shape: Shape, B: int, fold_launch: bool = False) -> dict:
+    """eegnet_launch_grids: {pass: number of trial ranges a batch of B is split into} for the train
+    step's passes A to E and the eval forward ("eval"; 0 for a fold launch).  Every range -- the
+    trials one workgroup (pass C for F1*D <= 16: one wave) runs in turn -- holds B // n or B // n + 1
+    trials.  ``fold_launch``: the
+    per-fold grids of ``train_step_folds``.  Host-side geometry only: nothing is launched."""
+    out = (ctypes.c_int * len(PASSES))()
+    _lib.check(_lib.load().eegnet_launch_grids(ctypes.byref(shape.dims(B)), ctypes.c_int(1 if fold_launch else 0),
+                                               out), "eegnet_launch_grids")
+    return dict(zip(PASSES, (int(v) for v in out)))
+
+
 def new_workspace(shape: Shape, B: int, device) -> torch.Tensor:
     nbytes = _lib.workspace_bytes(shape.dims(B))
     return torch.zeros(nbytes, dtype=torch.uint8, device=device)   # zero-filled once (tickets)

@@ -49,7 +49,9 @@ typedef struct eegnet_dims {
     int T;          /* samples per trial     (model.py:13 `T`)              */
     int F1;         /* temporal filters      (model.py:13, default 8)       */
     int D;          /* depth multiplier      (model.py:13, default 2)       */
-    int K1;         /* temporal kernel length (model.py:26: 32; 64 also supported) */
+    int K1;         /* temporal kernel length (model.py:26: 32; 64 also supported, except for
+                       training with F1*D > 16: eegnet_forward_train, _backward and _train_step
+                       return EEGNET_EINVAL for those dims, the eval forward takes them)  */
     float p_drop;   /* dropout p             (model.py:13, 50, 74)          */
     float bn_eps;   /* BatchNorm2d eps (1e-5)                               */
     float bn_momentum; /* BatchNorm2d momentum (0.1)                        */
@@ -310,6 +312,21 @@ size_t eegnet_trace_bytes(void);
  * units already; its kernels have the pitch T compiled in).  Every other entry point needs x_pitch = 0
  * or T.  No GPU needed. */
 int eegnet_x_pitch(const eegnet_dims* dims);
+
+/* How the launches split a batch of dims->B trials over workgroups: out[0..4] = the number of trial
+ * ranges of passes A, B, C, D, E of the train step, out[5] = of the eval forward (eegnet_forward_eval).
+ * A range is the set of trials one workgroup runs: contiguous rows [r B / n, (r + 1) B / n), one after
+ * the other, in the streaming passes (A, B, E, and D for F1*D <= 16); rows r, r + n, ... in the eval
+ * forward and the F1*D > 16 block-2 passes -- floor(B / n) or ceil(B / n) trials either way.  Pass C
+ * for F1*D <= 16 deals its trials to the w waves of its g workgroups (workgroup r, wave i: rows
+ * r w + i, + g w, ...): out[2] counts those per-wave streams, n = g w, each wave running its rows one
+ * after the other.  For F1*D > 16 the streaming passes (A, B's BN2 / ELU half,
+ * E) run ceil(F1*D / 16) chunk workgroups per range and the count is workgroups / chunks; pass B's
+ * block-2 half runs pass C's grid.  fold_launch != 0: the per-fold grids of eegnet_train_step_folds
+ * (F1*D <= 16; a function of dims->B alone, never of nfolds) and out[5] = 0.  Filled by the geometry
+ * code the launches themselves use; no launch, no allocation.  No GPU needed (256 CUs are assumed
+ * without one). */
+int eegnet_launch_grids(const eegnet_dims* dims, int fold_launch, int out[6]);
 
 /* 1 when `dims` run the wide kernels compiled for the EEGNet-16,4 64 x 512 geometry (compile-time
  * bounds and offsets), 0 when they run the generic wide / narrow kernels (for a wide K1 = 32 shape the

@@ -7,7 +7,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from golden_util import PARAM_NAMES
+from golden_util import PARAM_NAMES, assert_close, assert_grads_close
 from oracle import numpy_ref as nr
 
 M64 = (1 << 64) - 1
@@ -88,6 +88,60 @@ def oracle_eval(m, x):
     return logits
 
 
+def module_step(m, x_np, y_np, p, masks, what, dev):
+    """Module path on ``dev`` (model(x), CE, backward through the forward_train + backward kernels) with
+    injected masks against the float64 oracle step: logits, loss, all 12 grads, running statistics and
+    counters.  Returns the model (on ``dev``, after the step)."""
+    ref_logits, ref_loss, ref_grads, ref_nb, _ = oracle_step(m, x_np, y_np, p=p, masks=masks)
+    m = m.to(dev).train()
+    if masks is not None:
+        m.set_dropout_masks(torch.from_numpy(masks[0]).to(dev), torch.from_numpy(masks[1]).to(dev))
+    x = torch.from_numpy(np.ascontiguousarray(x_np, dtype=np.float32)).to(dev)
+    y = torch.from_numpy(y_np).to(dev)
+    logits = m(x)
+    loss = torch.nn.functional.cross_entropy(logits, y)
+    loss.backward()
+    assert_close(logits.detach().cpu().numpy(), ref_logits, name=f"{what} logits")
+    assert abs(float(loss) - ref_loss) <= 1e-4 * max(1.0, abs(ref_loss)), f"{what} loss"
+    assert_grads_close(grads_of(m), ref_grads, prefix=f"{what} grad.")
+    bufs = {k: b.detach().cpu().numpy() for k, b in m.named_buffers()}
+    for k, v in ref_nb.items():
+        if "running_mean" in k:
+            assert_close(bufs[k], v, atol_abs=1e-5 * max(1.0, float(np.abs(v).max())), name=f"{what} {k}")
+        elif "running_var" in k:
+            assert_close(bufs[k], v, name=f"{what} {k}")
+        else:
+            assert int(bufs[k]) == int(v), f"{what} {k}"
+    return m
+
+
+def oracle_train_loop(params, bufs, X, y, Xv, yv, epochs, seed):
+    """model.py:101-189 restated on the numpy oracle: per epoch, batches of 64 in the DataLoader
+    order for generator seed ``seed`` (dataset.epoch_permutation), forward/CE/backward/clamps/Adam;
+    validation in eval mode over batches of 64 (mean of batch CE means, accuracy)."""
+    from eegnetreplication_amd.dataset import epoch_permutation
+    st = nr.adam_init(params)
+    g = torch.Generator().manual_seed(seed)
+    tl, vl, va = [], [], []
+    for _ in range(epochs):
+        perm = epoch_permutation(len(y), g).numpy()
+        losses = []
+        for i in range(0, len(y), 64):
+            idx = perm[i:i + 64]
+            out = nr.train_step(params, bufs, X[idx], y[idx], st, p=0.0)
+            params, bufs = out["params"], out["buffers"]
+            losses.append(out["loss"])
+        tl.append(float(np.mean(losses)))
+        vls, correct = [], 0
+        for i in range(0, len(yv), 64):
+            lg, _, _ = nr.forward(params, bufs, Xv[i:i + 64], train=False)
+            vls.append(nr.cross_entropy(lg, yv[i:i + 64])[0])
+            correct += int((lg.argmax(1) == yv[i:i + 64]).sum())
+        vl.append(float(np.mean(vls)))
+        va.append(100 * correct / len(yv))
+    return params, bufs, tl, vl, va
+
+
 def grads_of(model):
     return {k: p.grad.detach().cpu().numpy() for k, p in model.named_parameters()}
 
@@ -101,4 +155,4 @@ def flat_to_dict(model, flat):
 
 
 __all__ = ["PARAM_NAMES", "device_masks", "random_model", "oracle_step", "oracle_eval",
-           "grads_of", "flat_to_dict", "state_np", "mix_key"]
+           "grads_of", "flat_to_dict", "state_np", "mix_key", "module_step", "oracle_train_loop"]

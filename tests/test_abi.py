@@ -175,6 +175,74 @@ def test_x_stats_width_matches_pass_a_row_head():
     assert lib.eegnet_x_stats_width(ctypes.byref(_lib.dims(64, 64, 512, F1=16, D=4))) < 0    # narrow path only
 
 
+def test_launch_grids_follow_the_documented_split():
+    """eegnet_launch_grids against the rule DESIGN 6 / eegnet_abi.h document, for the CU count the
+    library itself reports (the eval forward's grid at a batch far above it; 256 without a GPU):
+    streaming passes A, B, D, E over min(B, 2 CUs) workgroups and pass C and the eval forward over
+    min(B, CUs) for F1*D <= 16; for F1*D > 16 the streaming passes over min(B NOC, CUs) workgroups
+    rounded down to a multiple of NOC (of 8 NOC when it reaches that), NOC = ceil(F1*D / 16) per trial
+    range, and the block-2 passes and the eval forward over min(B, CUs); a fold launch gives a
+    workgroup 4 trials in the streaming passes and 16 in pass C.  Pass C of the F1*D <= 16 step is
+    counted in per-wave trial streams: workgroups x 8 waves at a runtime shape, x 16 at the compile-time
+    ones.  The trials per workgroup of fold launches and the waves of pass C are the default build's
+    values (a -DEEGNET_FOLD_TPW_* / -DEEGNET_B2 / -DEEGNET_D1 build has others)."""
+    from eegnetreplication_amd import _lib, ops
+    from eegnetreplication_amd.ops import Shape
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libeegnet_hip.so not built")
+    cus = ops.launch_grids(Shape(8, 64), 1 << 20)["eval"]
+    assert cus >= 1
+    batches = (1, 7, 64, 2 * cus + 3, 4 * cus + 3, 16 * cus)
+    for shape, nwc in ((Shape(8, 64), 8), (Shape(22, 257), 16)):
+        for B in batches:
+            s, c = min(B, 2 * cus), min(B, cus)
+            assert ops.launch_grids(shape, B) == dict(A=s, B=s, C=c * nwc, D=s, E=s, eval=c), (shape, B)
+            fs, fc = min(s, (B + 3) // 4), min(c, (B + 15) // 16)
+            assert ops.launch_grids(shape, B, fold_launch=True) == dict(A=fs, B=fs, C=fc * nwc, D=fs, E=fs,
+                                                                       eval=0), (shape, B)
+    wide = Shape(10, 128, F1=12, D=4)
+    noc = (wide.F2 + 15) // 16
+    for B in batches:
+        G = max(noc, min(B * noc, cus) // noc * noc)
+        if G >= 8 * noc:
+            G = G // (8 * noc) * (8 * noc)
+        r, c = G // noc, min(B, cus)
+        assert ops.launch_grids(wide, B) == dict(A=r, B=r, C=c, D=c, E=r, eval=c), B
+    with pytest.raises(RuntimeError, match="F1\\*D"):
+        ops.launch_grids(wide, 64, fold_launch=True)         # fold launches: the narrow path only
+    with pytest.raises(RuntimeError, match="B must be"):
+        ops.launch_grids(Shape(8, 64), 0)
+
+
+def test_wide_training_with_64_taps_is_rejected():
+    """F1*D > 16 with K1 = 64: eegnet_forward_train, eegnet_backward and eegnet_train_step refuse the
+    dims before they look at a pointer or launch anything (its train step ended in a GPU memory fault
+    whose cause is not known); eegnet_train_stage and eegnet_train_step_folds refuse every F1*D > 16.
+    The geometry calls and K1 = 32 are unaffected.  Runs without a GPU."""
+    import ctypes
+    from eegnetreplication_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libeegnet_hip.so not built")
+    lib = _lib.load()
+    d = _lib.dims(8, 5, 72, F1=8, D=4, K1=64)
+    assert _lib.workspace_bytes(d) > 0 and _lib.param_count(d) > 0
+    n = None                                         # never dereferenced: the calls fail on the dims
+    calls = {
+        "eegnet_forward_train": lambda dd: lib.eegnet_forward_train(ctypes.byref(dd), n, n, n, n, n, 1, 2, n, n, n, n),
+        "eegnet_backward": lambda dd: lib.eegnet_backward(ctypes.byref(dd), n, n, n, n, n, n, 1, 2, n, n, n, n, 0),
+        "eegnet_train_step": lambda dd: lib.eegnet_train_step(ctypes.byref(dd), n, n, n, n, 1, 2, n, n, n, 1e-3, 0.9,
+                                                              0.999, 1e-7, n, n, n, n, 0, n),
+    }
+    for name, call in calls.items():
+        assert call(d) == -1, name
+        msg = lib.eegnet_last_error().decode()
+        assert name in msg and "K1 = 64 is not supported" in msg, msg
+        assert call(_lib.dims(8, 5, 72, F1=8, D=4, K1=32)) == -1          # K1 = 32 gets as far as the NULL pointers
+        assert "is NULL" in lib.eegnet_last_error().decode(), name
+        assert call(_lib.dims(8, 3, 64, F1=8, D=2, K1=64)) == -1          # and so does F1*D <= 16 with 64 taps
+        assert "is NULL" in lib.eegnet_last_error().decode(), name
+
+
 def test_retired_persist_flag_is_rejected():
     """Round 5's opt-in one-launch persistent step (flag bit 4) is gone from the shipped library: the
     C-ABI rejects that bit (and every other unknown one) before any launch, so no caller -- FusedTrainer,

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from golden_util import PARAM_NAMES, assert_close, assert_params_close
+from hip_cases import oracle_train_loop as _oracle_train      # (shared with test_gpu_fold_oracle.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -120,34 +121,6 @@ def test_cli_refuses_missing_data_without_synthetic(tmp_path, monkeypatch):
 # ---------------------------------------------------------------------------------------------
 # train() over epochs vs a float64 oracle loop
 # ---------------------------------------------------------------------------------------------
-def _oracle_train(params, bufs, X, y, Xv, yv, epochs, seed):
-    """model.py:101-189 restated on the numpy oracle: per epoch, batches of 64 in the DataLoader
-    order for generator seed ``seed`` (dataset.epoch_permutation), forward/CE/backward/clamps/Adam;
-    validation in eval mode over batches of 64 (mean of batch CE means, accuracy)."""
-    from eegnetreplication_amd.dataset import epoch_permutation
-    from oracle import numpy_ref as nr
-    st = nr.adam_init(params)
-    g = torch.Generator().manual_seed(seed)
-    tl, vl, va = [], [], []
-    for _ in range(epochs):
-        perm = epoch_permutation(len(y), g).numpy()
-        losses = []
-        for i in range(0, len(y), 64):
-            idx = perm[i:i + 64]
-            out = nr.train_step(params, bufs, X[idx], y[idx], st, p=0.0)
-            params, bufs = out["params"], out["buffers"]
-            losses.append(out["loss"])
-        tl.append(float(np.mean(losses)))
-        vls, correct = [], 0
-        for i in range(0, len(yv), 64):
-            lg, _, _ = nr.forward(params, bufs, Xv[i:i + 64], train=False)
-            vls.append(nr.cross_entropy(lg, yv[i:i + 64])[0])
-            correct += int((lg.argmax(1) == yv[i:i + 64]).sum())
-        vl.append(float(np.mean(vls)))
-        va.append(100 * correct / len(yv))
-    return params, bufs, tl, vl, va
-
-
 @pytest.mark.parametrize("fused", [True, False])
 def test_train_loop_matches_oracle_over_epochs(fused):
     """3 epochs of train() on 150 trials of 22 x 257 (p = 0, batch 64 with a short last batch,

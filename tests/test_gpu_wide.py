@@ -18,7 +18,8 @@ import pytest
 import torch
 
 from golden_util import PARAM_NAMES, assert_close, assert_grads_close, assert_params_close, make_inputs, make_masks
-from hip_cases import device_masks, flat_to_dict, grads_of, oracle_eval, oracle_step, random_model
+from hip_cases import (device_masks, flat_to_dict, grads_of, module_step, oracle_eval, oracle_step,
+                       random_model)
 
 pytestmark = pytest.mark.gpu
 
@@ -30,28 +31,7 @@ def _dev():
 
 
 def _step(m, x_np, y_np, p, masks, what):
-    dev = _dev()
-    ref_logits, ref_loss, ref_grads, ref_nb, _ = oracle_step(m, x_np, y_np, p=p, masks=masks)
-    m = m.to(dev).train()
-    if masks is not None:
-        m.set_dropout_masks(torch.from_numpy(masks[0]).to(dev), torch.from_numpy(masks[1]).to(dev))
-    x = torch.from_numpy(np.ascontiguousarray(x_np, dtype=np.float32)).to(dev)
-    y = torch.from_numpy(y_np).to(dev)
-    logits = m(x)
-    loss = torch.nn.functional.cross_entropy(logits, y)
-    loss.backward()
-    assert_close(logits.detach().cpu().numpy(), ref_logits, name=f"{what} logits")
-    assert abs(float(loss) - ref_loss) <= 1e-4 * max(1.0, abs(ref_loss)), f"{what} loss"
-    assert_grads_close(grads_of(m), ref_grads, prefix=f"{what} grad.")
-    bufs = {k: b.detach().cpu().numpy() for k, b in m.named_buffers()}
-    for k, v in ref_nb.items():
-        if "running_mean" in k:
-            assert_close(bufs[k], v, atol_abs=1e-5 * max(1.0, float(np.abs(v).max())), name=f"{what} {k}")
-        elif "running_var" in k:
-            assert_close(bufs[k], v, name=f"{what} {k}")
-        else:
-            assert int(bufs[k]) == int(v), f"{what} {k}"
-    return m
+    return module_step(m, x_np, y_np, p, masks, what, _dev())     # (tests/hip_cases.py)
 
 
 @pytest.mark.parametrize("C,T,F1,D,B,p", [
