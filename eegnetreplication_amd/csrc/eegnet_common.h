@@ -54,8 +54,11 @@ struct Geo {
     int LP, RS;          // x / s / dy / e rows in LDS: left pad, row stride (floats, RS/4 odd)
     int TQ, NT16;        // ceil(T/4) quads, ceil(T/16) MFMA column tiles
     int RS2;             // block_2 rows (d2 / q / dq) stride
-    int RSW;             // per-wave block-2 rows of passes C / D (row_stride_b2)
-    int nwC, nwD;        // trial streams (waves) per workgroup of passes C / D
+    // rsv_*: unused, always 0 (where the removed pass-D / 256-thread variants kept RSW, nwD and gridB2).
+    // Kept: without them the later fields' kernarg offsets move, and k_frozen_reduce (66 -> 63 VGPRs),
+    // k_pass_e, k_wpass_e and k_infer_dx then come out with other register allocations and lengths
+    int rsv_rsw;
+    int nwC, rsv_nwd;    // nwC: trial streams (waves) per workgroup of pass C (k_pass_c)
     int CK, NCT, NKG;    // C padded to 4, ceil(C/16), ceil(T/16) k-groups of the dws GEMM
     int nH, nTl, nedge;  // lag-Gram edge terms: head pairs R(R+1)/2, tail pairs P(P+1)/2, + R + P sums
     float p, scale, eps, mom;
@@ -73,7 +76,7 @@ struct Geo {
     int nA, nB, nC, nD, nE;
     int QR;              // rows of pass E's lag correlation Q in its partial row: F1 when every wave's
                          // rows share one temporal group (narrow path, D = 2: summed before publishing), else F2
-    int grid;            // workgroups of passes C, D and the eval forward
+    int grid;            // workgroups of pass C (k_pass_c), the wide pass D and the eval-mode kernels
     int gridS;           // workgroups of the streaming passes A, B, D (k_pass_dr), E (two per CU)
     int gridA, gridE;    // passes A and E: gridS, or their own trials-per-workgroup in fold launches
     // LDS (floats)
@@ -83,7 +86,7 @@ struct Geo {
     unsigned long long* trace;
     // F2 > 16 (eegnet_wide.hip): o-chunks of 16 rows, Gram electrode slice per chunk, block-2 rows
     // padded to F2P (32 / 64), block-2 row stride; LDS (floats) of the wide kernels
-    int wide, NOC, CPC, F2P, RB, gridB2;
+    int wide, NOC, CPC, F2P, RB, rsv_gridb2;
     int gridW2;          // wide passes B2 and C (whole-job launches): two workgroups per CU at cfg5
     int splitC, splitD, splitE;   // wide passes whose reduction + finalize run in k_coltail (wide rows)
     int ldsWA, ldsWB, ldsWB2, ldsWC, ldsWD, ldsWE, ldsWI;
@@ -102,7 +105,7 @@ struct Geo {
 // (the bf16 eval kernel's kGeoCfg5 does the same, eegnet_infer_bf16.hip).
 #define EEG_SHAPE_W5(X)                                                                             \
     X(C, 64) X(T, 512) X(F1, 16) X(D, 4) X(F2, 64) X(K1, 32) X(P, 15) X(R, 16) X(T1, 128) X(T2, 16)  \
-    X(NF, 1024) X(LP, 16) X(RS, 548) X(TQ, 128) X(NT16, 32) X(RS2, 144) X(RSW, 156) X(CK, 64)       \
+    X(NF, 1024) X(LP, 16) X(RS, 548) X(TQ, 128) X(NT16, 32) X(RS2, 144) X(CK, 64)                   \
     X(NCT, 4) X(NKG, 32) X(nH, 136) X(nTl, 120) X(nedge, 287) X(o_w1, 0) X(o_g1, 512) X(o_b1, 528)   \
     X(o_ws, 544) X(o_g2, 4640) X(o_b2, 4704) X(o_w2, 4768) X(o_W3, 5792) X(o_g3, 9888) X(o_b3, 9952) \
     X(o_Wfc, 10016) X(o_bfc, 14112) X(nparam, 14116) X(nA, 448) X(nB, 128) X(nC, 4229) X(nD, 5248)    \
@@ -349,12 +352,6 @@ __host__ __device__ constexpr int row_stride(int K1, int T) {
     return ((rs / 4) & 1) ? rs : rs + 4;
 }
 __host__ __device__ constexpr int row_stride2(int T) { return rup4(LP2 + T / 4 + 8); }
-// per-wave block-2 rows of passes C / D (T1 = T/4 pooled samples): pads of 7 / 8 on the left and
-// room for the last 16-column MFMA group; RSW/4 odd so 16 rows read as float4 columns hit distinct banks
-__host__ __device__ constexpr int row_stride_b2(int T1) {
-    const int r = rup4(T1 + 24);
-    return ((r / 4) & 1) ? r : r + 4;
-}
 
 // compile-time row geometry for a temporal kernel length
 template <int K1>
@@ -470,13 +467,6 @@ __device__ __forceinline__ T ldc(const T* p) {
 __device__ __forceinline__ int opaque0() {
     int z = 0;
     asm volatile("" : "+s"(z));
-    return z;
-}
-// the same, ordered after `dep` is computed: chains row r's weight loads behind row r-1's result so
-// the compiler cannot hoist every row's loads to the top (asm volatile alone may all move up)
-__device__ __forceinline__ int opaque0_after(float dep) {
-    int z = 0;
-    asm volatile("" : "+s"(z) : "v"(dep));
     return z;
 }
 

@@ -121,9 +121,9 @@ __device__ __forceinline__ void xi_stage_elems(const GeoI& g, const uint16_t* __
 }
 
 // Compile-time geometry of BASELINE cfg5 (EEGNet-16,4 on 64ch x 512): the values make_geo_bf16
-// computes for those dims.  The host launches the CFG5 instantiation only when its runtime geometry
-// equals this one field for field (B, eps and dbg excepted), so every loop bound, stride and LDS
-// offset below folds to a constant there.
+// computes for those dims.  The host launches k_infer_bf16_cfg5 (eegnet_infer_bf16c.hip) only when its
+// runtime geometry equals this one field for field (B, eps and dbg excepted), so every loop bound,
+// stride and LDS offset folds to a constant there.
 constexpr GeoI kGeoCfg5 = {
     0, 64, 512, 16, 4, 64, 32, 15,          // B, C, T, F1, D, F2, K1, P
     64, 2, 64, 4, 64, 2, 512,               // CP, KC, F2P, NOT, F2K, KCW, TX
@@ -135,15 +135,10 @@ constexpr GeoI kGeoCfg5 = {
     145536,                                 // offF
     nullptr};
 
-template <int PFU, bool CFG5 = false>
-__global__ __launch_bounds__(NTI) void k_infer_bf16(GeoI gin, const float* __restrict__ prm,
+template <int PFU>
+__global__ __launch_bounds__(NTI) void k_infer_bf16(GeoI g, const float* __restrict__ prm,
                                                     const float* __restrict__ bn,
                                                     const uint16_t* __restrict__ x, float* __restrict__ logits) {
-    GeoI g = gin;
-    if constexpr (CFG5) {
-        g = kGeoCfg5;
-        g.B = gin.B; g.eps = gin.eps; g.dbg = gin.dbg;
-    }
     extern __shared__ __attribute__((aligned(16))) char smi[];
     char* const Xi = smi;                                   // x image (bf16, swizzled)
     float* const Aa = reinterpret_cast<float*>(smi);        // pooled rows a (fp32), aliases Xi

@@ -42,15 +42,13 @@ __device__ __forceinline__ void block2_rows(int F2, int T1, int RS2, const float
 }
 
 // ================================================================================================
-// Block-2-rate passes C and D: one trial per wave.  Lane t holds pooled sample t (+64 m) of all F2
-// rows, so block_2's pointwise mix, BN3, ELU and the backward elementwise chain are lane-local
-// register work with wave-uniform (scalar) weights, and the two depthwise 1x16 convolutions take
-// their neighbours from DPP lane shifts (wave_shr / wave_shl).  No workgroup barrier inside the
-// trial loop: the waves of a workgroup are independent trial streams until the final reduction.
+// Block-2-rate pass C: one trial per wave.  Lane t holds pooled sample t (+64 m) of all F2 rows, so
+// BN3, ELU and the backward elementwise chain are lane-local register work with wave-uniform
+// (scalar) weights.  No workgroup barrier inside the trial loop: the waves of a workgroup are
+// independent trial streams until the final reduction.  (Pass D, k_pass_dr below, works in the
+// streaming passes' row layout and takes its 1x16 convolution's neighbours from DPP lane shifts.)
 // ================================================================================================
-constexpr int NTHS = 512;       // workgroup bound of pass D and of the runtime-shape pass C
-constexpr int LPQ = 8;          // left pad of pass D's LDS rows (16-byte aligned MFMA / window reads)
-constexpr int LPD = 7;          // left pad of pass D's d2 rows: d2p[t + k - 7] sits at [t + k]
+constexpr int NTHS = 512;       // workgroup bound of the runtime-shape pass C
 constexpr int MAXNFQ = 8;       // flattened head features per lane: F2*(T/32) <= 512
 
 // 8-lane sums of consecutive lanes: after the three DPP steps lanes 8i+4..8i+7 hold the sum of
@@ -91,31 +89,9 @@ __device__ __forceinline__ void shl1(float (&x)[MQ], int lane) {
     }
 }
 
-// transposed depthwise 1x16: y[t] = sum_k w[k] x[t + 7 - k] (the input gradient of the 'same' conv, model.py:54-61)
-template <int MQ>
-__device__ __forceinline__ void conv16_same_t(const float (&x)[MQ], const float* __restrict__ w, float (&y)[MQ],
-                                              int lane) {
-    float s[MQ];
-#pragma unroll
-    for (int m = 0; m < MQ; ++m) { y[m] = w[7] * x[m]; s[m] = x[m]; }
-#pragma unroll
-    for (int k = 6; k >= 0; --k) {                 // s = x[t + 7 - k]
-        shl1<MQ>(s, lane);
-#pragma unroll
-        for (int m = 0; m < MQ; ++m) y[m] = fmaf(w[k], s[m], y[m]);
-    }
-#pragma unroll
-    for (int m = 0; m < MQ; ++m) s[m] = x[m];
-#pragma unroll
-    for (int k = 8; k < K2; ++k) {                 // s = x[t - (k - 7)]
-        shr1<MQ>(s, lane);
-#pragma unroll
-        for (int m = 0; m < MQ; ++m) y[m] = fmaf(w[k], s[m], y[m]);
-    }
-}
-
-// the same as two independent chains (taps 0-7 over left shifts, 8-15 over right shifts) added at
-// the end: half the dependent-latency chain per row
+// transposed depthwise 1x16: y[t] = sum_k w[k] x[t + 7 - k] (the input gradient of the 'same' conv,
+// model.py:54-61), as two independent chains (taps 0-7 over left shifts, 8-15 over right shifts) added
+// at the end: half the dependent-latency chain per row
 template <int MQ>
 __device__ __forceinline__ void conv16_same_t2(const float (&x)[MQ], const float* __restrict__ w, float (&y)[MQ],
                                                int lane) {
@@ -147,18 +123,6 @@ __device__ __forceinline__ void load_rows(const float* __restrict__ src, int b, 
             const int t = lane + 64 * m;
             d[o][m] = (o < F2 && t < T1) ? base[o * T1 + t] : 0.f;
         }
-}
-
-// xh[j] = BN3-normalised r[j] (batch statistics of finalize 2), r from pass B's r plane
-template <int MQ>
-__device__ __forceinline__ void bn3_rows(const float* coef, int F2, const float (&r)[F2MAX][MQ],
-                                         float (&xh)[F2MAX][MQ]) {
-#pragma unroll
-    for (int j = 0; j < F2MAX; ++j) {
-        const float mu3 = j < F2 ? coef[CF_MU3 * CSTR + j] : 0.f, inv3 = j < F2 ? coef[CF_INV3 * CSTR + j] : 0.f;
-#pragma unroll
-        for (int m = 0; m < MQ; ++m) xh[j][m] = (r[j][m] - mu3) * inv3;
-    }
 }
 
 // ================================================================================================
@@ -400,282 +364,13 @@ __global__ __launch_bounds__(TT ? NTH : NTHS) void k_pass_c(Geo g, const float* 
     pass_c_body<K1, CC, TT, FF, FOLD>(g, prm, coef, r3g, mask3, dlin, labels, logits, dlout, part, mode, fa, fc, sm);
 }
 
-#if EEGNET_D1
 // ================================================================================================
-// Pass D: block_2 backward (dW3, dw2), dp2 = d(pooled ELU output), BN2-backward sums.
-// (rounds 1-5; built only by -DEEGNET_D1=1 A/B builds since k_pass_dr replaced it)
-// part row: [dW3 F2*F2][dw2 F2*16][Sdz2 F2][Sdz2x F2]
-// Per-wave LDS rows (stride RSW): P0 d2 (pad LPD) | P1 q, then dq (pad LPQ) | P2 dr (pad LPQ) | Hs [NF].
-// ================================================================================================
-// MASK = false: dropout from the device generator only (mask2 / mask3 are null).  The host-mask
-// path costs registers in this kernel (256 VGPRs + spills against 156), so it is its own instantiation.
-template <int K1, int CC, int TT, int FF, bool FOLD = false, bool MASK = true>
-__global__ __launch_bounds__(NTHS) void k_pass_d(Geo g, const float* __restrict__ prm,
-                                                 const float* coef,    // the finalize writes it: no __restrict__
-                                                 const float* __restrict__ d2g,
-                                                 const float* __restrict__ E1g,
-                                                 const float* __restrict__ E2g,
-                                                 const float* __restrict__ q3g,
-                                                 const float* __restrict__ r3g,
-                                                 const uint8_t* __restrict__ mask2,
-                                                 const uint8_t* __restrict__ mask3,
-                                                 const float* __restrict__ dl,
-                                                 float* __restrict__ dp2g, float* __restrict__ part,
-                                                 FinArgs fa, FoldCall fc) {
-    EEG_DIMS(g);
-    TRACE(g, 3, TR_ENTRY);
-    unsigned dk0, dk1;
-    if (FOLD) {
-        const eegnet_fold f = fold_rec(fc);
-        char* ws = (char*)f.ws;
-        prm = f.params;
-        coef = (const float*)(ws + fc.off.coef);
-        d2g = (const float*)(ws + fc.off.d2);
-        E1g = (const float*)(ws + fc.off.E1); E2g = (const float*)(ws + fc.off.E2);
-        q3g = (const float*)(ws + fc.off.q3); r3g = (const float*)(ws + fc.off.r3);
-        mask2 = nullptr; mask3 = nullptr;
-        dl = (const float*)(ws + fc.off.dl);
-        dp2g = (float*)(ws + fc.off.dp2);
-        part = (float*)(ws + fc.off.partD);
-        fa = fold_fin(fc, f, TK_D, 0, 0, false, false, g.nparam);
-        dk0 = fold_drop_key(fc, f, 0);
-        dk1 = fold_drop_key(fc, f, 1);
-    } else {
-        dk0 = drop_key(g, 0);
-        dk1 = drop_key(g, 1);
-    }
-    if constexpr (!MASK) { mask2 = nullptr; mask3 = nullptr; }
-    constexpr int MQ = TT ? (TT / 4 + 63) / 64 : MAXT1Q;
-    constexpr int NFQ = (TT && FF) ? (FF * (TT / 32) + 63) / 64 : MAXNFQ;
-    const int RSW = TT ? row_stride_b2(TT / 4) : g.RSW;
-    const int NFP = rup4(NF);
-    const int nw = blockDim.x >> 6;
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int li = lane & 15, lk = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    float* P0 = sm + wave * (3 * F2 * RSW + NFP);
-    float* P1 = P0 + F2 * RSW;
-    float* P2 = P1 + F2 * RSW;
-    float* Hs = P2 + F2 * RSW;
-
-    for (int i = lane; i < 3 * F2 * RSW; i += 64) P0[i] = 0.f;   // pads stay zero
-    float wf[NCLS][NFQ];
-#pragma unroll
-    for (int n = 0; n < NCLS; ++n)
-#pragma unroll
-        for (int u = 0; u < NFQ; ++u) {
-            const int i = lane + 64 * u;
-            wf[n][u] = i < NF ? prm[g.o_Wfc + n * NF + i] : 0.f;
-        }
-    floatx4 acc3 = {0.f, 0.f, 0.f, 0.f};        // dW3 tile: D[j = 4 lk + r][i = li]
-    const int o2 = lane >> 2, kq = lane & 3;   // dw2 item of this lane: row o2, taps 4 kq .. 4 kq + 3
-    float acc2[4] = {0.f, 0.f, 0.f, 0.f};
-    float sz[2 * F2MAX];                       // [Sdz2 F2MAX][Sdz2x F2MAX], per-lane partials
-#pragma unroll
-    for (int j = 0; j < 2 * F2MAX; ++j) sz[j] = 0.f;
-    const int nkg = (T1 + 15) >> 4, ntq = (T1 + 3) >> 2;
-    wave_lds_fence();
-
-    TRACE(g, 3, TR_PRO);
-    TRACE_DECL();
-    drain_prologue_loads();
-    // a trial's pass-B rows (d2, q, r) and dlogits go out together -- one global round trip, not three
-    // -- and the next trial's are loaded into the same registers as soon as this trial has consumed
-    // them (after the BN3 backward), so they land during the dW3 / dq / dw2 / dd2 phases
-    float dlv[NCLS];
-    float d[F2MAX][MQ], q[F2MAX][MQ], r[F2MAX][MQ];
-    auto load_trial = [&](int bb) {
-#pragma unroll
-        for (int n = 0; n < NCLS; ++n) dlv[n] = dl[(size_t)bb * NCLS + n];
-        load_rows<MQ>(d2g, bb, F2, T1, lane, d);
-        load_rows<MQ>(q3g, bb, F2, T1, lane, q);
-        load_rows<MQ>(r3g, bb, F2, T1, lane, r);
-    };
-    const int bstep = gridDim.x * nw;
-    if (blockIdx.x * nw + wave < g.B) load_trial(blockIdx.x * nw + wave);
-    for (int b = blockIdx.x * nw + wave; b < g.B; b += bstep) {
-        // d2 rows -> P0 (read back by the dw2 correlation)
-#pragma unroll
-        for (int o = 0; o < F2MAX; ++o)
-#pragma unroll
-            for (int m = 0; m < MQ; ++m) {
-                const int t = lane + 64 * m;
-                if (o < F2 && t < T1) P0[o * RSW + LPD + t] = d[o][m];
-            }
-        // dh -> dropout -> dp3 (flattened) into Hs
-#pragma unroll
-        for (int u = 0; u < NFQ; ++u) {
-            const int i = lane + 64 * u;
-            float dd = 0.f;
-#pragma unroll
-            for (int n = 0; n < NCLS; ++n) dd = fmaf(dlv[n], wf[n][u], dd);
-            if (i < NF) Hs[i] = dd * keep_mul(g, mask3, dk1, (unsigned)(b * NF + i));
-        }
-        TRACE_PH(g, 3, 0, tph_);
-        // block-2 depthwise output (pass B's q plane) -> P1
-#pragma unroll
-        for (int o = 0; o < F2MAX; ++o)
-#pragma unroll
-            for (int m = 0; m < MQ; ++m) {
-                const int t = lane + 64 * m;
-                if (o < F2 && t < T1) P1[o * RSW + LPQ + t] = q[o][m];
-            }
-        wave_lds_fence();
-        TRACE_PH(g, 3, 1, tph_);
-        // BN3 backward with the batch constants of finalize 3: dr = A3 dz3 + B3 + C3 xh3,
-        // dz3 = dp3/8 * ELU'(z3); zero beyond T1 (the dq / dd2 shifts read it)
-        float dr[F2MAX][MQ];
-        {
-            float xh[F2MAX][MQ];
-            bn3_rows<MQ>(coef, F2, r, xh);          // r: pass B's pointwise output
-#pragma unroll
-            for (int j = 0; j < F2MAX; ++j) {
-                if (j < F2) {
-                    const int oz = opaque0();
-                    const float g3 = prm[g.o_g3 + j + oz], b3 = prm[g.o_b3 + j + oz];
-                    const float A3 = coef[CF_A3 * CSTR + j + oz], B3 = coef[CF_B3 * CSTR + j + oz];
-                    const float C3 = coef[CF_C3 * CSTR + j + oz];
-#pragma unroll
-                    for (int m = 0; m < MQ; ++m) {
-                        const int t = lane + 64 * m;
-                        const float dz = t < 8 * T2 ? Hs[j * T2 + (t >> 3)] * 0.125f * elu_d(fmaf(g3, xh[j][m], b3)) : 0.f;
-                        dr[j][m] = t < T1 ? fmaf(A3, dz, fmaf(C3, xh[j][m], B3)) : 0.f;
-                        if (t < T1) P2[j * RSW + LPQ + t] = dr[j][m];
-                    }
-                } else {
-#pragma unroll
-                    for (int m = 0; m < MQ; ++m) dr[j][m] = 0.f;
-                }
-            }
-        }
-        wave_lds_fence();
-        TRACE_PH(g, 3, 2, tph_);
-        // E1 / E2 of pass B for the BN2-backward sums at the end (issued here, consumed last), then
-        // the next trial's rows (younger: the E1 / E2 wait does not wait for them)
-        float e1v[F2MAX][MQ], e2v[F2MAX][MQ];
-        load_rows<MQ>(E1g, b, F2, T1, lane, e1v);
-        load_rows<MQ>(E2g, b, F2, T1, lane, e2v);
-        if (b + bstep < g.B) load_trial(b + bstep);
-        // dW3[j][i] += sum_t dr[j][t] q[i][t] on the matrix cores (float4 k-permuted operands)
-        {
-            // (ds_read_b64 operands, t = 16 kg + 2 lk + {0, 1}, + 8: conflict-free, as pass E's dws GEMM)
-            const bool on = li < F2;
-            const float* ar = P2 + (on ? li : 0) * RSW + LPQ + 2 * lk;
-            const float* br = P1 + (on ? li : 0) * RSW + LPQ + 2 * lk;
-            for (int kg = 0; kg < nkg; ++kg) {
-                floatx2 a0 = lds_ld2(ar + 16 * kg), a1 = lds_ld2(ar + 16 * kg + 8);
-                floatx2 b0 = lds_ld2(br + 16 * kg), b1 = lds_ld2(br + 16 * kg + 8);
-                if (!on) { a0 = (floatx2){0.f, 0.f}; a1 = a0; b0 = a0; b1 = a0; }
-                acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[0], b0[0], acc3, 0, 0, 0);
-                acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[1], b0[1], acc3, 0, 0, 0);
-                acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[0], b1[0], acc3, 0, 0, 0);
-                acc3 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[1], b1[1], acc3, 0, 0, 0);
-            }
-        }
-        wave_lds_fence();                          // q rows consumed before dq overwrites them
-        TRACE_PH(g, 3, 3, tph_);
-        // dq[i][t] = sum_j W3[j][i] dr[j][t] (registers, and P1 for the dw2 correlation)
-        float dq[F2MAX][MQ];
-#pragma unroll
-        for (int i = 0; i < F2MAX; ++i) {
-            if (i < F2) {
-                const int oz = i >= 2 ? opaque0_after(dq[i >= 2 ? i - 2 : 0][0]) : opaque0();
-                const float* w3c = prm + (g.o_W3 + i + oz);      // column i of W3 (stride F2)
-#pragma unroll
-                for (int m = 0; m < MQ; ++m) {
-                    const int t = lane + 64 * m;
-                    float a = 0.f;
-#pragma unroll
-                    for (int j = 0; j < F2MAX; ++j)
-                        if (j < F2) a = fmaf(w3c[j * F2], dr[j][m], a);
-                    dq[i][m] = a;
-                    if (t < T1) P1[i * RSW + LPQ + t] = a;
-                }
-            } else {
-#pragma unroll
-                for (int m = 0; m < MQ; ++m) dq[i][m] = 0.f;
-            }
-        }
-        wave_lds_fence();
-        TRACE_PH(g, 3, 4, tph_);
-        // dw2[o][k] += sum_t dq[o][t] d2p[o][t+k-7]: lane -> (row o2, taps 4 kq + kk), loop over t
-        if (o2 < F2) {
-            const float* dqr = P1 + o2 * RSW + LPQ;
-            const float* d2r = P0 + o2 * RSW + 4 * kq;      // d2p[t + k - 7] = P0[row + t + k]
-            for (int tq = 0; tq < ntq; ++tq) {
-                const floatx4 a4 = lds_ld4(dqr + 4 * tq);
-                const floatx4 w0 = lds_ld4(d2r + 4 * tq), w1 = lds_ld4(d2r + 4 * tq + 4);
-                const float w[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc2[kk] = fmaf(a4[i], w[i + kk], acc2[kk]);
-            }
-        }
-        TRACE_PH(g, 3, 5, tph_);
-        // dd2 = conv16_same_t(dq) -> dropout -> dp2; BN2-backward sums (E1/E2 of pass B)
-        const size_t rb = (size_t)b * F2 * T1;
-#pragma unroll
-        for (int o = 0; o < F2MAX; ++o) {
-            if (o >= F2) continue;
-            float a[MQ];
-            const int oz = o >= 2 ? opaque0_after(sz[o >= 2 ? o - 2 : 0]) : opaque0();
-            conv16_same_t<MQ>(dq[o], prm + (g.o_w2 + o * K2 + oz), a, lane);
-#pragma unroll
-            for (int m = 0; m < MQ; ++m) {
-                const int t = lane + 64 * m;
-                if (t < T1) {
-                    const int gi = o * T1 + t;
-                    const float dp = a[m] * keep_mul(g, mask2, dk0, (unsigned)(rb + gi));
-                    st_pol<EEGNET_NT_MID>(dp, dp2g + rb + gi);
-                    sz[o] = fmaf(dp * 0.25f, e1v[o][m], sz[o]);
-                    sz[F2MAX + o] = fmaf(dp * 0.25f, e2v[o][m], sz[F2MAX + o]);
-                }
-            }
-        }
-        wave_lds_fence();
-        TRACE_PH(g, 3, 6, tph_);
-    }
-    TRACE_LOOP(g, 3);
-    // ---- workgroup reduction ----
-    __syncthreads();
-    float* red = sm;                         // [nw][nD]
-    float* rw = red + wave * g.nD;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int j = 4 * lk + r;
-        if (j < F2 && li < F2) rw[j * F2 + li] = acc3[r];
-    }
-    if (o2 < F2) {
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) rw[F2 * F2 + o2 * K2 + 4 * kq + kk] = acc2[kk];
-    }
-    wave_reduce<2 * F2MAX>(sz);
-    if ((lane & 15) == 0) {
-        const int r0 = (lane >> 4) * (F2MAX / 2);
-#pragma unroll
-        for (int j = 0; j < F2MAX / 2; ++j) {
-            const int idx = j + r0;
-            if (idx < F2MAX) { if (idx < F2) rw[F2 * F2 + 16 * F2 + idx] = sz[j]; }
-            else if (idx - F2MAX < F2) rw[F2 * F2 + 17 * F2 + idx - F2MAX] = sz[j];
-        }
-    }
-    __syncthreads();
-    float* row = part + (size_t)blockIdx.x * g.nD;
-    for (int c = tid; c < g.nD; c += blockDim.x) pub(row + c, wave_rows_sum<NTHS / 64>(red, nw, g.nD, c));
-    double* dsm = (double*)sm;
-    if (grid_reduce(g, part, g.nD, fa, dsm)) { fin4(g, prm, dsm + 2, fa); TRACE(g, 3, TR_FIN); }
-}
-#endif  // EEGNET_D1
-
-// ================================================================================================
-// Pass D in the streaming passes' row layout (k_pass_dr, the default; k_pass_d above is the
-// -DEEGNET_D1=1 build).  k_pass_d gives each wave a whole trial, so one trial is a ~12 us serial chain
-// of one wave at two waves per SIMD (225 VGPRs): scalar weight loads chained row after row, the
-// pointwise mix over 16 rows in one lane, and 16 conv rows back to back.  Here the workgroup works on
-// one trial at a time like passes B and E: wave w owns rows o = 2w, 2w + 1 of the trial's [F2, T1]
-// planes, lane t owns pooled sample t (+ 64 m), two 512-thread workgroups per CU.
+// Pass D: block_2 backward (dW3, dw2), dp2 = d(pooled ELU output), BN2-backward sums, in the streaming
+// passes' row layout.  (Rounds 1-5 gave each wave a whole trial, a ~12 us serial chain of one wave at
+// two waves per SIMD: scalar weight loads chained row after row, the pointwise mix over 16 rows in one
+// lane, and 16 conv rows back to back)  Here the workgroup works on one trial at a time
+// like passes B and E: wave w owns rows o = 2w, 2w + 1 of the trial's [F2, T1] planes, lane t owns
+// pooled sample t (+ 64 m), two 512-thread workgroups per CU.
 //   step 1 (row-local): BN3 backward of the own rows -> dr rows and the q rows into LDS (alternate
 //     buffers per trial, so one barrier per trial)
 //   barrier
@@ -684,7 +379,7 @@ __global__ __launch_bounds__(NTHS) void k_pass_d(Geo g, const float* __restrict_
 //     shifts), dropout -> dp2, BN2-backward sums
 // The trial's five plane rows per lane and its dlogits come a trial ahead (registers / SGPRs); the
 // block-2 weights sit in LDS and reach the SGPRs by readfirstlane.
-// part row: [dW3 F2*F2][dw2 F2*16][Sdz2 F2][Sdz2x F2] (k_pass_d's, finalize 4 unchanged)
+// part row: [dW3 F2*F2][dw2 F2*16][Sdz2 F2][Sdz2x F2] (finalize 4)
 // LDS: dr rows x 2 | q rows x 2 (F2MAX rows of RSD floats) | W3^T [F2MAX][F2MAX] | w2 [F2MAX][16]
 // ================================================================================================
 // row stride 64 MQ + 2: a 32-lane group of the MFMA operand reads (16 rows x 2 consecutive k) covers

@@ -777,34 +777,16 @@ __device__ __forceinline__ void b2_bn3(const float* coef, const B2Map& mp, float
 // (PC_BWD) CE, classifier grads, BN3-bwd sums.  Partial row [dWfc 4*NF][dbfc 4][Sdz3 F2][Sdz3x F2][loss].
 // LDS: H [NF] (features, then their gradients) | class partials [(NT / 64)][4] | sums | XH [F2P][RB]
 // ================================================================================================
-template <int NT, bool FOLD = false, bool SPEC = false>
+template <int NT, bool SPEC = false>
 __global__ __launch_bounds__(NT, (SPEC && NT == 512) ? 4 : 1) void k_wpass_c(Geo gin, const float* __restrict__ prm, const float* coef,
                                                   const float* __restrict__ r3g, const uint8_t* __restrict__ mask3,
                                                   const float* __restrict__ dlin, const int64_t* __restrict__ labels,
                                                   float* __restrict__ logits, float* __restrict__ dlout,
-                                                  float* __restrict__ part, int mode, FinArgs fa, FoldCall fc) {
+                                                  float* __restrict__ part, int mode, FinArgs fa) {
     const Geo g = geo_w<SPEC>(gin);
     const int F2 = g.F2, F2P = g.F2P, T1 = g.T1, T2 = g.T2, NF = g.NF, RB = g.RB;
     const int NJT = F2P >> 4, NT1 = (T1 + 15) >> 4;
-    unsigned dk1;
-    const int64_t* perm = nullptr;                     // fold launches: labels through the permutation
-    long long row0 = 0;
-    if (FOLD) {                                        // fold-indexed launch: this fold's pointers
-        const eegnet_fold f = fold_rec(fc);
-        char* ws = (char*)f.ws;
-        prm = f.params;
-        coef = (const float*)(ws + fc.off.coef);
-        r3g = (const float*)(ws + fc.off.r3);
-        mask3 = nullptr; dlin = nullptr; logits = nullptr;
-        labels = f.labels;
-        perm = f.perm; row0 = fc.row0;
-        dlout = (float*)(ws + fc.off.dl);
-        part = (float*)(ws + fc.off.partC);
-        fa = fold_fin(fc, f, TK_C, 0, 1, false, false, g.nparam);
-        dk1 = fold_drop_key(fc, f, 1);
-    } else {
-        dk1 = drop_key(g, 1);
-    }
+    const unsigned dk1 = drop_key(g, 1);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* H = sm;
     float* lgs = H + ((NF + 3) & ~3);
@@ -906,7 +888,7 @@ __global__ __launch_bounds__(NT, (SPEC && NT == 512) ? 4 : 1) void k_wpass_c(Geo
 #pragma unroll
                 for (int n = 0; n < NCLS; ++n) se += expf(L[n] - mx);
                 const float lse = mx + logf(se);
-                const int y = (int)labels[fold_row(perm, row0, b)];
+                const int y = (int)labels[b];
                 const float Ly = y == 0 ? L[0] : y == 1 ? L[1] : y == 2 ? L[2] : L[3];
                 if (tid == 0) lossacc += lse - Ly;
 #pragma unroll
@@ -993,37 +975,17 @@ __global__ __launch_bounds__(NT, (SPEC && NT == 512) ? 4 : 1) void k_wpass_c(Geo
 // [dW3 F2*F2][dw2 F2*16][Sdz2 F2][Sdz2x F2].
 // LDS: D2 [F2P][RB] | Q [F2P][RB] (q, then dq) | DR [F2P][RB] | W2s | Hd [NF] | item sums
 // ================================================================================================
-template <int NT, bool FOLD = false, bool SPEC = false>
+template <int NT, bool SPEC = false>
 __global__ __launch_bounds__(NT, 2) void k_wpass_d(Geo gin, const float* __restrict__ prm, const float* coef,
                                                   const float* __restrict__ d2g, const float* __restrict__ E1g,
                                                   const float* __restrict__ E2g, const float* __restrict__ q3g,
                                                   const float* __restrict__ r3g, const uint8_t* __restrict__ mask2,
                                                   const uint8_t* __restrict__ mask3, const float* __restrict__ dl,
-                                                  float* __restrict__ dp2g, float* __restrict__ part, FinArgs fa,
-                                                  FoldCall fc) {
+                                                  float* __restrict__ dp2g, float* __restrict__ part, FinArgs fa) {
     const Geo g = geo_w<SPEC>(gin);
     const int F2 = g.F2, F2P = g.F2P, T1 = g.T1, T2 = g.T2, NF = g.NF, RB = g.RB;
     const int NJT = F2P >> 4, KS3 = F2P >> 2, NT1 = (T1 + 15) >> 4, TQ1 = (T1 + 3) >> 2;
-    unsigned dk0, dk1;
-    if (FOLD) {
-        const eegnet_fold f = fold_rec(fc);
-        char* ws = (char*)f.ws;
-        prm = f.params;
-        coef = (const float*)(ws + fc.off.coef);
-        d2g = (const float*)(ws + fc.off.d2);
-        E1g = (const float*)(ws + fc.off.E1); E2g = (const float*)(ws + fc.off.E2);
-        q3g = (const float*)(ws + fc.off.q3); r3g = (const float*)(ws + fc.off.r3);
-        mask2 = nullptr; mask3 = nullptr;
-        dl = (const float*)(ws + fc.off.dl);
-        dp2g = (float*)(ws + fc.off.dp2);
-        part = (float*)(ws + fc.off.partD);
-        fa = fold_fin(fc, f, TK_D, 0, 0, false, false, g.nparam);
-        dk0 = fold_drop_key(fc, f, 0);
-        dk1 = fold_drop_key(fc, f, 1);
-    } else {
-        dk0 = drop_key(g, 0);
-        dk1 = drop_key(g, 1);
-    }
+    const unsigned dk0 = drop_key(g, 0), dk1 = drop_key(g, 1);
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* D2 = sm;
     float* Q = D2 + F2P * RB;

@@ -185,7 +185,7 @@ def test_launch_grids_follow_the_documented_split():
     workgroup 4 trials in the streaming passes and 16 in pass C.  Pass C of the F1*D <= 16 step is
     counted in per-wave trial streams: workgroups x 8 waves at a runtime shape, x 16 at the compile-time
     ones.  The trials per workgroup of fold launches and the waves of pass C are the default build's
-    values (a -DEEGNET_FOLD_TPW_* / -DEEGNET_B2 / -DEEGNET_D1 build has others)."""
+    values (a -DEEGNET_FOLD_TPW_* build has others)."""
     from eegnetreplication_amd import _lib, ops
     from eegnetreplication_amd.ops import Shape
     if not os.path.exists(_lib.LIB_PATH):
