@@ -993,6 +993,8 @@ __global__ __launch_bounds__(NTB, WPEB) void k_pass_b(Geo g, const float* __rest
 // tiles | lag tiles
 // Per trial: x DMA (for this trial's dws GEMM) | dy2 from v -> dy rows | lag correlation (dy, s) and
 // FIR^T (dy -> e, in place) | barrier | next trial's s / dp2 DMA and v loads | dws GEMM (e, x) | barrier
+// 22 x 256 (PIPEE): held dy2 -> dy rows | x DMA | lag correlation and FIR^T | next s DMA | barrier |
+// dws GEMM with the next trial's dy2 (-> registers) spread through it | dp2 DMA two trials on | barrier
 // ================================================================================================
 // EEGNET_LDSX_E = n (counter builds only, wrong results): drop one class of pass E's LDS accesses to
 // read its share of SQ_LDS_BANK_CONFLICT (tools/lds_probe.sh): 1 dp2 reads, 2 FIR^T windows, 3 lag
@@ -1059,11 +1061,35 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     float* const Eb = EINPL ? Dys : Ss;
     constexpr bool XDMA_ = TT != 0;
     constexpr bool DPDMA_ = XDMA_ && FF && ((FF * (TT / 4)) % 256 == 0);
-    // the specialised pipeline (EEGNet-8,2 at T = 256): every wave DMAs its own rows of the next
-    // trial's dp2 (right after its dy2 phase) and s (right after its lag correlation), the next v is
-    // loaded a whole trial ahead, and the first barrier waits only for this trial's x
+    // the specialised pipeline (EEGNet-8,2 at T = 256): dy2 of the next trial is computed under this
+    // trial's dws GEMM and held in registers; every wave DMAs its own rows of the next trial's s (right
+    // after its lag correlation) and of the dp2 two trials on (right after the dy2 that read them), the
+    // next v is loaded at the top of the trial, and the first barrier waits only for this trial's x
     constexpr bool PIPEE = ONEOC && XDMA_ && DPDMA_ && (TT / 4 == 64) && (TT == 256);
     float sdyl = 0.f, sdyvl = 0.f;                   // this lane's row (half-wave) sums of dy, dy v
+    // dy2 = A dz2 + B + C xh2 (BN2 backward) of this lane's row: its constants (CT, after the prologue's
+    // barrier), the two pooled dp2 values under octet oc, and one sample from its v (added to the sums)
+    struct Dy2C { float alh, beh, gah, bth, Aoh, Boh, Coh; };
+    auto dy2_consts = [&]() {
+        const floatx4 c0 = lds_ld4(CT + 8 * oh), c1 = lds_ld4(CT + 8 * oh + 4);
+        return Dy2C{c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2]};
+    };
+    auto dy2_dp = [&](int oc, float (&dpq)[2]) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            dpq[h] = EEGNET_LDSX_E == 1 ? 0.01f * (oc + h) : (2 * oc + h < T1) ? DP[oh * T1 + 2 * oc + h] * 0.25f : 0.f;
+    };
+    auto dy2_at = [&](const Dy2C& k, float vin, float dq, bool in) {
+        const float v = in ? vin : 0.f;
+        const float xh = fmaf(k.alh, v, k.beh);
+        const float z = fmaf(k.gah, xh, k.bth);
+        const float dz = dq * elu_d(z);
+        float d = fmaf(k.Aoh, dz, fmaf(k.Coh, xh, k.Boh));
+        d = in ? d : 0.f;
+        sdyl += d;
+        sdyvl = fmaf(d, v, sdyvl);
+        return d;
+    };
     // dW1 lag correlation Q[o][k] = sum_t dy[o][t] s[o][t+k-P] on the matrix cores.  With t = 16a + u
     // and s'[i] = s[i-P]:
     //     Cq[u][w] = sum_a dy[16a+u] s'[16a+w]        (16 x 16 NWT, K = the 16-sample blocks a)
@@ -1174,68 +1200,81 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     TRACE(g, 4, TR_PRO);
     TRACE_DECL();
     drain_prologue_loads();
+    // The specialised pipeline keeps dy2 one trial ahead, in registers: dy2(b + 1) is computed while the
+    // dws GEMM of trial b waits on its operands (every input is there by then: v(b + 1) in vpf, this
+    // wave's dp2(b + 1) rows, CT) and is stored to the wave's dy rows at the top of trial b + 1, once the
+    // closing barrier says that every wave has read trial b's e rows.  The sums take the trials in the
+    // same order as the in-place form did.  The wave's dp2 rows run two trials ahead, DMA'd as soon as
+    // dy2 has read them; v(b + 1) is loaded at the top of trial b, where dy2(b) has left vpf free -- the
+    // loop's one load site, as before (a second one here, behind the drain, was waited for at the copies
+    // the register allocator put between the two sites' registers: a round trip per workgroup).
+    float dyh[PIPEE ? 8 : 1];
+    auto dp2_ahead = [&](int bb) {                         // this wave's dp2 rows of trial bb
+        wave_lds_fence();                                  // its reads of the rows are done
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            const int o = RPW * wave + r;
+            if (EEGNET_LDSX_E != 7) dma4(dp2g + (size_t)bb * ndp + o * T1 + lane, DP + o * T1);
+        }
+    };
+    if constexpr (PIPEE) {
+        if (b0 < b1) {
+            const Dy2C k = dy2_consts();
+            float dpq[2];
+            dy2_dp(fir_oct(lane), dpq);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) dyh[i] = dy2_at(k, vpf[0][i], dpq[i >> 2], true);
+            if (b0 + 1 < b1) dp2_ahead(b0 + 1);
+        }
+    }
     for (int b = b0; b < b1; ++b) {
         const int bn = b + 1;
         pace_prio(b - b0, b1 - b0);
-        float vc[MO][8];
-        if constexpr (VPF) {
-#pragma unroll
-            for (int m = 0; m < MO; ++m)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) vc[m][i] = vpf[m][i];
-            if constexpr (PIPEE)
-                if (bn < b1) v_load<MO>(vg, bn, F2, NO, oh, lane, vpf);
+        if constexpr (PIPEE) {
+            const int oc = fir_oct(lane);
+            if (EEGNET_LDSX_E != 5)
+                lds_st_oct(Dys + oh * RS + LP + 8 * oc, oc, (floatx4){dyh[0], dyh[1], dyh[2], dyh[3]},
+                           (floatx4){dyh[4], dyh[5], dyh[6], dyh[7]});
+            if (bn < b1) v_load<MO>(vg, bn, F2, NO, oh, lane, vpf);
+            TRACE_PH(g, 4, 0, tph_);
+            wave_lds_fence();                              // dy rows complete
+            TRACE_PH(g, 4, 1, tph_);
         } else {
-            v_load<MO>(vg, b, F2, NO, oh, lane, vc);
-        }
-        TRACE_PH(g, 4, 0, tph_);
-        // dy2 = A dz2 + B + C xh2 (BN2 backward) of this lane's octets; sums of dy and dy v
-        if (oh < F2) {
-            float* drow = Dys + oh * RS + LP;
-            const floatx4 c0 = lds_ld4(CT + 8 * oh), c1 = lds_ld4(CT + 8 * oh + 4);
-            const float alh = c0[0], beh = c0[1], gah = c0[2], bth = c0[3];
-            const float Aoh = c1[0], Boh = c1[1], Coh = c1[2];
+            float vc[MO][8];
+            if constexpr (VPF) {
 #pragma unroll
-            for (int m = 0; m < MO; ++m) {
-                const int oc = fir_oct(lane) + 32 * m;
-                if (oc >= NO) break;
-                float dpq[2];
+                for (int m = 0; m < MO; ++m)
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    dpq[h] = EEGNET_LDSX_E == 1 ? 0.01f * (oc + h) : (2 * oc + h < T1) ? DP[oh * T1 + 2 * oc + h] * 0.25f : 0.f;
-                float dy[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const bool in = 8 * oc + i < T;
-                    const float v = in ? vc[m][i] : 0.f;
-                    const float xh = fmaf(alh, v, beh);
-                    const float z = fmaf(gah, xh, bth);
-                    const float dz = dpq[i >> 2] * elu_d(z);
-                    float d = fmaf(Aoh, dz, fmaf(Coh, xh, Boh));
-                    d = in ? d : 0.f;
-                    dy[i] = d;
-                    sdyl += d;
-                    sdyvl = fmaf(d, v, sdyvl);
-                }
-                if (EEGNET_LDSX_E != 5)
-                    lds_st_oct(drow + 8 * oc, oc, (floatx4){dy[0], dy[1], dy[2], dy[3]}, (floatx4){dy[4], dy[5], dy[6], dy[7]});
+                    for (int i = 0; i < 8; ++i) vc[m][i] = vpf[m][i];
+            } else {
+                v_load<MO>(vg, b, F2, NO, oh, lane, vc);
             }
-        }
-        TRACE_PH(g, 4, 1, tph_);
-        wave_lds_fence();                                  // dy rows complete, this wave's dp2 rows read
-        if constexpr (PIPEE) {                             // next trial's dp2 rows of this wave
-            if (bn < b1) {
+            TRACE_PH(g, 4, 0, tph_);
+            // dy2 of this lane's octets; sums of dy and dy v
+            if (oh < F2) {
+                float* drow = Dys + oh * RS + LP;
+                const Dy2C k = dy2_consts();
 #pragma unroll
-                for (int r = 0; r < RPW; ++r) {
-                    const int o = RPW * wave + r;
-                    if (EEGNET_LDSX_E != 7) dma4(dp2g + (size_t)bn * ndp + o * T1 + lane, DP + o * T1);
+                for (int m = 0; m < MO; ++m) {
+                    const int oc = fir_oct(lane) + 32 * m;
+                    if (oc >= NO) break;
+                    float dpq[2];
+                    dy2_dp(oc, dpq);
+                    float dy[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) dy[i] = dy2_at(k, vc[m][i], dpq[i >> 2], 8 * oc + i < T);
+                    if (EEGNET_LDSX_E != 5)
+                        lds_st_oct(drow + 8 * oc, oc, (floatx4){dy[0], dy[1], dy[2], dy[3]}, (floatx4){dy[4], dy[5], dy[6], dy[7]});
                 }
             }
+            TRACE_PH(g, 4, 1, tph_);
+            wave_lds_fence();                              // dy rows complete, this wave's dp2 rows read
         }
         // this trial's x rows for the dws GEMM (the buffer was last read by the previous trial's
         // GEMM); they land during the lag correlation / FIR^T, by the next barrier
         if constexpr (XDMA)
-            if (EEGNET_LDSX_E != 7) x_dma_asm(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
+            if (EEGNET_LDSX_E != 7)
+                x_dma_asm(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
         TRACE_PH(g, 4, 2, tph_);
         {
             float tl[K1];
@@ -1281,6 +1320,11 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                 if (EEGNET_LDSX_E != 6)
                     lds_st_oct(erow + 8 * oc, oc, (floatx4){e[0], e[1], e[2], e[3]}, (floatx4){e[4], e[5], e[6], e[7]});
                 if constexpr (PIPEE) {                     // next trial's s rows of this wave
+                    // v(b + 1) is taken from its loads here, on every path to the GEMM phase: they went
+                    // out at the top of the trial, but the compiler's wait for them at a first use behind
+                    // the s DMAs (vmcnt is in order, and it counts no asm DMA) would wait for those too
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(vpf[0][i]));
                     if (bn < b1 && EEGNET_LDSX_E != 7) {
 #pragma unroll
                         for (int r = 0; r < RPW; ++r) {
@@ -1418,6 +1462,47 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                 const int lo = 64 * (lk & 1) + 4 * (lk >> 1);
                 const float* arow = Eb + (aon ? li : 0) * RS + LP + lo;
                 const float* brow = Xb + (bon ? c : li) * RS + LP + lo;
+                if constexpr (PIPEE) {
+                    // The wave's k-groups are a compile-time count here (NT16 = 16 over the 4 waves of a
+                    // c-tile: 4), so every operand read issues before the first MFMA -- one LDS round
+                    // trip instead of one per k-group -- and the one accumulator chain keeps its k order.
+                    // dy2 of the next trial is spread through the chain (an element per two MFMAs): it
+                    // fills the operand wait and the chain's dependent issue, and leaves dy in registers
+                    // (other waves read e from the dy rows until the closing barrier).
+                    constexpr int NCTC = (CC + 15) / 16, WPC = NWB / NCTC, KGW = ((TT + 15) / 16) / WPC;
+                    static_assert(WPC * NCTC == NWB && KGW * WPC == (TT + 15) / 16 && KGW * WPC <= KGP && 8 % KGW == 0 &&
+                                  4 * KGW == 2 * 8, "dws GEMM split of the pipelined shape");
+                    const int to0 = 128 * (kg0 >> 3) + 8 * (kg0 & 7);      // kg0 = KGW part_: kg0 & 7 + j < 8
+                    auto gemm = [&](auto ahead) {
+                        floatx4 a4[KGW], b4[KGW];
+#pragma unroll
+                        for (int j = 0; j < KGW; ++j) {
+                            if (EEGNET_LDSX_E == 4) {
+                                a4[j] = (floatx4){0.01f * (kg0 + j), 0.02f * li, 0.f, 1.f};
+                                b4[j] = (floatx4){0.03f * (kg0 + j), 0.01f * lk, 1.f, 0.f};
+                            } else {
+                                a4[j] = lds_ld4(arow + to0 + 8 * j);
+                                b4[j] = lds_ld4(brow + to0 + 8 * j);
+                            }
+                            if (!aon) a4[j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+                            if (!bon) b4[j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+                        }
+                        Dy2C k = {};
+                        float dpq[2] = {0.f, 0.f};
+                        if constexpr (decltype(ahead)::value) {
+                            k = dy2_consts();
+                            dy2_dp(fir_oct(lane), dpq);
+                        }
+#pragma unroll
+                        for (int n = 0; n < 4 * KGW; ++n) {
+                            xacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[n >> 2][n & 3], b4[n >> 2][n & 3], xacc, 0, 0, 0);
+                            if constexpr (decltype(ahead)::value)
+                                if (n & 1) dyh[n >> 1] = dy2_at(k, vpf[0][n >> 1], dpq[n >> 3], true);
+                        }
+                    };
+                    if (bn < b1) gemm(std::true_type{});
+                    else gemm(std::false_type{});
+                } else
                 for (int kg = kg0; kg < kg1; ++kg) {
                     const int to = kg < KGP ? 128 * (kg >> 3) + 8 * (kg & 7) : 16 * kg + 4 * lk - lo;
                     floatx4 a4, b4;
@@ -1464,12 +1549,25 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                 }
             }
         }
+        if constexpr (PIPEE)
+            if (bn + 1 < b1) dp2_ahead(bn + 1);            // dy2(b + 1) has read dp2(b + 1)
         TRACE_PH(g, 4, 6, tph_);
         // (without DMA the next trial's x rows are stored right after the barrier: the next reader of
         // the x buffer is that trial's dws GEMM, behind its first barrier)
         // e, x rows consumed; next s rows and dp2 staged.  With both by DMA the barrier waits for the
         // DMA only: the 2 MO v loads issued after it stay in flight into the next trial.
-        if constexpr (PIPEE) barrier_vm<0>();
+        // The pipeline's vmcnt windows, from the wave's issue order over a trial b (b + 2 < b1):
+        //     end of trial b - 1:  dp2(b + 1) x RPW                 (b = b0: after the prologue's drain)
+        //     top of trial b:      v(b + 1) x 2 MO, x(b) x 2..3
+        //     after the FIR^T:     s(b + 1) x RPW                   mid barrier: vmcnt(RPW) -- all but s(b + 1)
+        //     after the GEMM:      dp2(b + 2) x RPW                 closing barrier: vmcnt(RPW) -- s(b + 1),
+        // read by this wave's lag correlation at the top of trial b + 1, has landed; dp2(b + 2) stays in
+        // flight until the next mid barrier.  The last trial's mid barrier and the last two trials' closing
+        // barriers have nothing behind what they wait for: vmcnt(0).
+        if constexpr (PIPEE) {
+            if (bn + 1 < b1) barrier_vm<RPW>();
+            else barrier_vm<0>();
+        }
         else if constexpr (XDMA && DPDMA && VPF) barrier_vm<2 * MO>();
         else if constexpr (XDMA || DPDMA) barrier_vm<0>();
         else __syncthreads();
