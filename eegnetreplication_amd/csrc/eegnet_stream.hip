@@ -991,10 +991,16 @@ __global__ __launch_bounds__(NTB, WPEB) void k_pass_b(Geo g, const float* __rest
 // part row: [Q F2*K1][Xm F2*C][Sdy F2][Sdyv F2]
 // LDS: s rows | dy rows, then e rows | x rows | dp2 [F2][T1] | BN2 constants; after the loop: dws
 // tiles | lag tiles
-// Per trial: x DMA (for this trial's dws GEMM) | dy2 from v -> dy rows | lag correlation (dy, s) and
-// FIR^T (dy -> e, in place) | barrier | next trial's s / dp2 DMA and v loads | dws GEMM (e, x) | barrier
-// 22 x 256 (PIPEE): held dy2 -> dy rows | x DMA | lag correlation and FIR^T | next s DMA | barrier |
-// dws GEMM with the next trial's dy2 (-> registers) spread through it | dp2 DMA two trials on | barrier
+// Three per-trial pipelines, one trial loop each behind the shared prologue (pass_e_body's DMA / PIPE):
+// Register-staged (the runtime shapes <32,0,0,0> and <64,0,0,0>).  Per trial: v load | dy2 from v -> dy
+// rows | lag correlation (dy, s) | FIR^T (dy -> e, to the s rows) | next dp2 loads | barrier | next s / x
+// loads (registers) | dws GEMM (e, x; ds_read_b64) | dp2 stores | barrier | x / s stores
+// DMA (22 x 257).  Per trial: dy2 from the prefetched v -> dy rows | x DMA (for this trial's dws GEMM) |
+// lag correlation (dy, s) | FIR^T (dy -> e, in place) | barrier | next trial's s / dp2 DMA and v loads |
+// dws GEMM (e, x; ds_read_b128) | barrier
+// PIPE (22 x 256).  Per trial: held dy2 -> dy rows, next v loads | x DMA | lag correlation and FIR^T,
+// fused | next s DMA | barrier | dws GEMM with the next trial's dy2 (-> registers) spread through it | dp2
+// DMA two trials on | barrier
 // ================================================================================================
 // EEGNET_LDSX_E = n (counter builds only, wrong results): drop one class of pass E's LDS accesses to
 // read its share of SQ_LDS_BANK_CONFLICT (tools/lds_probe.sh): 1 dp2 reads, 2 FIR^T windows, 3 lag
@@ -1012,6 +1018,24 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     using G_ = KG<K1>;
     EEG_DIMS_NT(g, NTB);
     const int XP = EEG_XP(TT, g);
+    // The two pipeline flags (header comment).  DMA: compile-time shapes; x, s and dp2 rows go by LDS-DMA,
+    // v is prefetched into registers and e overwrites the dy rows in place (the next trial's s rows land
+    // during the dws GEMM), against register staging, __syncthreads and e in the s rows without it.
+    // PIPE: EEGNet-8,2 at T = 256, one octet per lane and every row live; dy2 runs one trial ahead in
+    // registers, each wave DMAs its own s and dp2 rows, lag correlation and FIR^T are one block.
+    constexpr bool DMA = TT != 0;
+    constexpr bool PIPE = TT == 256;
+    static_assert(!DMA || (CC && FF), "LDS-DMA staging is specialised to compile-time C and F2");
+    static_assert(!DMA || (FF * (TT / 4)) % 256 == 0, "the dp2 DMA moves whole 256-float pieces");
+    static_assert(!DMA || FF == RPW * NWB, "every row of every wave is live");
+    static_assert(!DMA || TT / 128 >= 2, "the ds_read_b128 dws GEMM takes whole 128-sample blocks first");
+    static_assert(!PIPE || (EEG_NO(TT) <= 32 && TT / 4 == 64), "one octet and one dp2 DMA lane per lane");
+    // PIPE's dws GEMM split: NCTC c-tiles, WPC waves on each, KGW k-groups per wave (KGP: the k-groups
+    // in whole 128-sample blocks)
+    constexpr int KGP = 8 * (TT / 128);
+    constexpr int NCTC = (CC + 15) / 16, WPC = PIPE ? NWB / NCTC : 0, KGW = PIPE ? ((TT + 15) / 16) / WPC : 0;
+    static_assert(!PIPE || (WPC * NCTC == NWB && KGW * WPC == (TT + 15) / 16 && KGW * WPC <= KGP && 8 % KGW == 0 &&
+                            4 * KGW == 2 * 8), "dws GEMM split of the pipelined shape");
     TRACE(g, 4, TR_ENTRY);
     const int64_t* perm = nullptr;                 // fold launches: trial rows through the permutation
     long long row0 = 0;
@@ -1041,32 +1065,16 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     int b0, b1;
     trial_range(g, b0, b1);
     const int li = lane & 15, lk = lane >> 4;
-    constexpr bool XDMA = TT != 0;                    // compile-time shapes: x / s rows by LDS-DMA
-    static_assert(!XDMA || (CC && FF), "LDS-DMA staging is specialised to compile-time C and F2");
 
     TRACE_PS(g, 0);
-    if constexpr (!XDMA) zero_fill<false>(sm, (2 * F2 + C) * RS, F2, RS, LP, T, tid);
+    if constexpr (!DMA) zero_fill<false>(sm, (2 * F2 + C) * RS, F2, RS, LP, T, tid);
     TRACE_PS(g, 1);
     float tap[NTS][K1];
     float* CT = DP + ((F2 * T1 + 3) & ~3);       // BN2 forward / backward constants per row, [F2][8]
     const int NO = EEG_NO(TT);
     constexpr int MO = EEG_MO(TT);
     const int hr = fir_row(lane), oh = RPW * wave + hr;
-    // specialised shapes with one octet per lane and every row live: e overwrites the dy rows in place;
-    // otherwise e goes to the s rows
-    constexpr bool ONEOC = FF && TT && (EEG_NO(TT) <= 32) && (FF == RPW * NWB);
-    // with the s rows staged by DMA (the next trial's land during the dws GEMM) e must not go to them:
-    // it overwrites the dy rows in place, from registers once every read of the row is done
-    constexpr bool EINPL = ONEOC || XDMA;
-    float* const Eb = EINPL ? Dys : Ss;
-    constexpr bool XDMA_ = TT != 0;
-    constexpr bool DPDMA_ = XDMA_ && FF && ((FF * (TT / 4)) % 256 == 0);
-    // the specialised pipeline (EEGNet-8,2 at T = 256): dy2 of the next trial is computed under this
-    // trial's dws GEMM and held in registers; every wave DMAs its own rows of the next trial's s (right
-    // after its lag correlation) and of the dp2 two trials on (right after the dy2 that read them), the
-    // next v is loaded at the top of the trial, and the first barrier waits only for this trial's x
-    constexpr bool PIPEE = ONEOC && XDMA_ && DPDMA_ && (TT / 4 == 64) && (TT == 256);
-    float sdyl = 0.f, sdyvl = 0.f;                   // this lane's row (half-wave) sums of dy, dy v
+    float sdyl = 0.f, sdyvl = 0.f;                  // this lane's row (half-wave) sums of dy, dy v
     // dy2 = A dz2 + B + C xh2 (BN2 backward) of this lane's row: its constants (CT, after the prologue's
     // barrier), the two pooled dp2 values under octet oc, and one sample from its v (added to the sums)
     struct Dy2C { float alh, beh, gah, bth, Aoh, Boh, Coh; };
@@ -1108,52 +1116,43 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     const int ct = gemm_on ? wave / wpc : 0, part_ = gemm_on ? wave - ct * wpc : 0;
     const int kg0 = (NT16 * part_) / wpc, kg1 = gemm_on ? (NT16 * (part_ + 1)) / wpc : 0;
     floatx4 xacc = {0.f, 0.f, 0.f, 0.f};
-    // without DMA (T % 256 != 0) x rows are staged through registers (pfx, during the dws GEMM) and
-    // each wave stages its own s rows (RPW rows, MS samples per lane per row), so only
-    // the wave itself reads them before its next barrier (the lag correlation reads own rows)
-    constexpr int MS = TT ? (TT + 63) / 64 : 16;
-    float pws[XDMA ? 1 : RPW][XDMA ? 1 : MS];
+    // The register-staged pipeline's staging registers (no DMA instantiation touches them).  x rows go
+    // through pfx during the dws GEMM; each wave stages its own s rows (pws: RPW rows, MS samples per lane
+    // per row), so only the wave itself reads them before its next barrier (the lag correlation reads own
+    // rows); the dp2 rows of the next trial ride along in pdp, one trial ahead: a synchronous load would
+    // wait (vmcnt is in order) for every memory operation issued before it
+    constexpr int MS = 16, NDP = 8;              // F2 * T1 <= NDP * NTB
+    float pws[RPW][MS], pfx[PF], pdp[NDP];
     auto s_rows_load = [&](int bb) {
-        if constexpr (!XDMA) {
 #pragma unroll
-            for (int r = 0; r < RPW; ++r) {
-                const float* src = sg + ((size_t)bb * F2 + min(RPW * wave + r, F2 - 1)) * s_pitch(T);
+        for (int r = 0; r < RPW; ++r) {
+            const float* src = sg + ((size_t)bb * F2 + min(RPW * wave + r, F2 - 1)) * s_pitch(T);
 #pragma unroll
-                for (int k = 0; k < MS; ++k) pws[r][k] = src[min(lane + 64 * k, T - 1)];
-            }
+            for (int k = 0; k < MS; ++k) pws[r][k] = src[min(lane + 64 * k, T - 1)];
         }
     };
     auto s_rows_put = [&]() {
-        if constexpr (!XDMA) {
 #pragma unroll
-            for (int r = 0; r < RPW; ++r) {
-                const int o = RPW * wave + r;
+        for (int r = 0; r < RPW; ++r) {
+            const int o = RPW * wave + r;
 #pragma unroll
-                for (int k = 0; k < MS; ++k)
-                    if (o < F2 && lane + 64 * k < T) Ss[o * RS + LP + lane + 64 * k] = pws[r][k];
-            }
+            for (int k = 0; k < MS; ++k)
+                if (o < F2 && lane + 64 * k < T) Ss[o * RS + LP + lane + 64 * k] = pws[r][k];
         }
     };
-    float pfx[XDMA ? 1 : PF];
-    // v of the next trial: registers, loaded after the FIR^T (DMA shapes; the others load it at the
-    // top of the trial, keeping registers for the register-staged x and s rows)
-    constexpr bool VPF = XDMA;
+    // DMA and PIPE: v of the next trial, in registers (DMA loads it after the FIR^T, PIPE at the top of
+    // the trial; the register-staged pipeline loads v at the top of its own trial, keeping registers
+    // for the staged x and s rows)
     float vpf[MO][8];
-    // dp2 rows of the next trial ride along (registers, one trial ahead): a synchronous load would
-    // wait (vmcnt is in order) for every memory operation issued before it
-    constexpr int NDP = (CC && TT) ? (FF * (TT / 4) + NTB - 1) / NTB : 8;   // F2 * T1 <= NDP * NTB
     const int ndp = F2 * T1;
-    float pdp[NDP];
-    // specialised shapes: dp2 rows go straight to LDS by DMA (no registers, no exposed load)
-    constexpr bool DPDMA = TT && FF && ((FF * (TT / 4)) % 256 == 0);
-    // compile-time shapes: the first trial's s / dp2 rows go out by LDS-DMA and its v into registers
+    // DMA and PIPE: the first trial's s / dp2 rows go out by LDS-DMA and its v into registers
     // before anything else; the pad fill, the tap / coefficient loads overlap them and one barrier
     // waits for all of it (in sequence these were four dependent round trips, ~6 us of prologue)
     if (b0 < b1) {
-        if constexpr (XDMA) s_dma_asm(sg + (size_t)b0 * F2 * s_pitch(T), F2, T, RS, LP, Ss, wave, lane);
+        if constexpr (DMA) s_dma_asm(sg + (size_t)b0 * F2 * s_pitch(T), F2, T, RS, LP, Ss, wave, lane);
         else s_rows_load(b0);
         TRACE_PS(g, 3);
-        if constexpr (DPDMA) flat_dma_asm(dp2g + (size_t)b0 * ndp, ndp, DP, wave, lane);
+        if constexpr (DMA) flat_dma_asm(dp2g + (size_t)b0 * ndp, ndp, DP, wave, lane);
         else {
 #pragma unroll
             for (int j = 0; j < NDP; ++j) pdp[j] = dp2g[(size_t)b0 * ndp + min(tid + NTB * j, ndp - 1)];
@@ -1162,10 +1161,10 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                 if (tid + NTB * j < ndp) DP[tid + NTB * j] = pdp[j];
             for (int i = tid + NTB * NDP; i < ndp; i += NTB) DP[i] = dp2g[(size_t)b0 * ndp + i];
         }
-        if constexpr (VPF) v_load<MO>(vg, b0, F2, NO, oh, lane, vpf);
+        if constexpr (DMA) v_load<MO>(vg, b0, F2, NO, oh, lane, vpf);
         TRACE_PS(g, 4);
     }
-    if constexpr (XDMA) zero_pads(sm, 2 * F2 + C, RS, LP, T, tid);   // the data windows are DMA'd / written
+    if constexpr (DMA) zero_pads(sm, 2 * F2 + C, RS, LP, T, tid);   // the data windows are DMA'd / written
     load_taps<K1, NTS>(g, prm, D, F2, wave, tap);
     TRACE_PS(g, 2);
     {   // the BN2 forward / backward constants of this wave's rows [o][8], by scalar loads (ldc: not
@@ -1186,9 +1185,9 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     }
     adam_scalars_publish(g, fa);
     const int step0 = adam_step0(g, fa);   // before the reduction ticket (adam_slice)
-    if constexpr (XDMA) barrier_vm<0>();          // first s / dp2 landed (asm DMA), pads and tables written
+    if constexpr (DMA) barrier_vm<0>();           // first s / dp2 landed (asm DMA), pads and tables written
     else __syncthreads();
-    if constexpr (!XDMA) {
+    if constexpr (!DMA) {
         if (b0 < b1) {
             s_rows_put();
             x_prefetch<PF, NTB>(x + fold_row(perm, row0, b0) * (C * XP), C, T, pfx, tid);
@@ -1200,24 +1199,51 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     TRACE(g, 4, TR_PRO);
     TRACE_DECL();
     drain_prologue_loads();
-    // The specialised pipeline keeps dy2 one trial ahead, in registers: dy2(b + 1) is computed while the
-    // dws GEMM of trial b waits on its operands (every input is there by then: v(b + 1) in vpf, this
-    // wave's dp2(b + 1) rows, CT) and is stored to the wave's dy rows at the top of trial b + 1, once the
-    // closing barrier says that every wave has read trial b's e rows.  The sums take the trials in the
-    // same order as the in-place form did.  The wave's dp2 rows run two trials ahead, DMA'd as soon as
-    // dy2 has read them; v(b + 1) is loaded at the top of trial b, where dy2(b) has left vpf free -- the
-    // loop's one load site, as before (a second one here, behind the drain, was waited for at the copies
-    // the register allocator put between the two sites' registers: a round trip per workgroup).
-    float dyh[PIPEE ? 8 : 1];
-    auto dp2_ahead = [&](int bb) {                         // this wave's dp2 rows of trial bb
-        wave_lds_fence();                                  // its reads of the rows are done
+
+    // One trial loop per pipeline, each in the order its wave executes.  What the loops share beyond the
+    // dy2 lambdas above -- the dy2 stage and the lag correlation of the register-staged and DMA loops, the
+    // operand rows of the two ds_read_b128 GEMMs -- is the same text in each: behind a lambda or an inlined
+    // function the compiler promotes cq and xacc to registers in another order, and the register
+    // allocation of every instantiation moves with it (profiles/r9_refactor_compare.txt).
+    // The dws GEMM, Xm[o][c] += sum_t e[o][t] x[c][t] on the matrix cores (16 e rows x 16 x rows of this
+    // wave's c-tile; the k order inside the wave's t range is permuted identically in A and B), has one
+    // form per loop.  PIPE and DMA read their operands (e is in the dy rows) by ds_read_b128:
+    // k-group kg of a 128-sample block: lane lk takes the float4 at t = 128 (kg >> 3) +
+    // 8 (kg & 7) + 64 (lk & 1) + 4 (lk >> 1), one ds_read_b128 per operand.  The 16-lane
+    // groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...) pair lk = 0 with 1 and 2 with 3, whose
+    // offsets now agree mod 64 floats (one bank row): a group is 16 distinct rows li, each on
+    // its own 4-bank slot (RS / 4 odd) -- conflict-free at one instruction per operand (the
+    // plain t = 16 kg + 4 lk order was 2-way; two ds_read_b64 per operand are conflict-free
+    // but cost more issue than the conflicts did)
+    // (a lane past the last channel reads -- and zeroes -- row li, not row 0: row 0 shares
+    // its 4-bank slot with row 16, which lane li = 0 of the second c-tile reads)
+    if constexpr (PIPE) {
+        // ---- PIPE (22 x 256) ----
+        // dy2 runs one trial ahead, in registers: dy2(b + 1) is computed while the dws GEMM of trial b waits
+        // on its operands (every input is there by then: v(b + 1) in vpf, this wave's dp2(b + 1) rows, CT)
+        // and is stored to the wave's dy rows at the top of trial b + 1, once the closing barrier says
+        // that every wave has read trial b's e rows.  The sums take the trials in the
+        // same order as the in-place form did.  The wave's dp2 rows run two trials ahead, DMA'd as soon as
+        // dy2 has read them; v(b + 1) is loaded at the top of trial b, where dy2(b) has left vpf free -- the
+        // loop's one load site, as before (a second one here, behind the drain, was waited for at the copies
+        // the register allocator put between the two sites' registers: a round trip per workgroup).
+        // The vmcnt windows, from the wave's issue order over a trial b (b + 2 < b1):
+        //     end of trial b - 1:  dp2(b + 1) x RPW                 (b = b0: after the prologue's drain)
+        //     top of trial b:      v(b + 1) x 2 MO, x(b) x 2..3
+        //     after the FIR^T:     s(b + 1) x RPW                   mid barrier: vmcnt(RPW) -- all but s(b + 1)
+        //     after the GEMM:      dp2(b + 2) x RPW                 closing barrier: vmcnt(RPW) -- s(b + 1),
+        // read by this wave's lag correlation at the top of trial b + 1, has landed; dp2(b + 2) stays in
+        // flight until the next mid barrier.  The last trial's mid barrier and the last two trials' closing
+        // barriers have nothing behind what they wait for: vmcnt(0).
+        float dyh[8];
+        auto dp2_ahead = [&](int bb) {                         // this wave's dp2 rows of trial bb
+            wave_lds_fence();                                  // its reads of the rows are done
 #pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-            const int o = RPW * wave + r;
-            if (EEGNET_LDSX_E != 7) dma4(dp2g + (size_t)bb * ndp + o * T1 + lane, DP + o * T1);
-        }
-    };
-    if constexpr (PIPEE) {
+            for (int r = 0; r < RPW; ++r) {
+                const int o = RPW * wave + r;
+                if (EEGNET_LDSX_E != 7) dma4(dp2g + (size_t)bb * ndp + o * T1 + lane, DP + o * T1);
+            }
+        };
         if (b0 < b1) {
             const Dy2C k = dy2_consts();
             float dpq[2];
@@ -1226,64 +1252,31 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
             for (int i = 0; i < 8; ++i) dyh[i] = dy2_at(k, vpf[0][i], dpq[i >> 2], true);
             if (b0 + 1 < b1) dp2_ahead(b0 + 1);
         }
-    }
-    for (int b = b0; b < b1; ++b) {
-        const int bn = b + 1;
-        pace_prio(b - b0, b1 - b0);
-        if constexpr (PIPEE) {
-            const int oc = fir_oct(lane);
-            if (EEGNET_LDSX_E != 5)
-                lds_st_oct(Dys + oh * RS + LP + 8 * oc, oc, (floatx4){dyh[0], dyh[1], dyh[2], dyh[3]},
-                           (floatx4){dyh[4], dyh[5], dyh[6], dyh[7]});
-            if (bn < b1) v_load<MO>(vg, bn, F2, NO, oh, lane, vpf);
-            TRACE_PH(g, 4, 0, tph_);
-            wave_lds_fence();                              // dy rows complete
-            TRACE_PH(g, 4, 1, tph_);
-        } else {
-            float vc[MO][8];
-            if constexpr (VPF) {
-#pragma unroll
-                for (int m = 0; m < MO; ++m)
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) vc[m][i] = vpf[m][i];
-            } else {
-                v_load<MO>(vg, b, F2, NO, oh, lane, vc);
+        for (int b = b0; b < b1; ++b) {
+            const int bn = b + 1;
+            pace_prio(b - b0, b1 - b0);
+            {   // held dy2 -> dy rows, next v loads
+                const int oc = fir_oct(lane);
+                if (EEGNET_LDSX_E != 5)
+                    lds_st_oct(Dys + oh * RS + LP + 8 * oc, oc, (floatx4){dyh[0], dyh[1], dyh[2], dyh[3]},
+                               (floatx4){dyh[4], dyh[5], dyh[6], dyh[7]});
+                if (bn < b1) v_load<MO>(vg, bn, F2, NO, oh, lane, vpf);
+                TRACE_PH(g, 4, 0, tph_);
+                wave_lds_fence();                              // dy rows complete
+                TRACE_PH(g, 4, 1, tph_);
             }
-            TRACE_PH(g, 4, 0, tph_);
-            // dy2 of this lane's octets; sums of dy and dy v
-            if (oh < F2) {
-                float* drow = Dys + oh * RS + LP;
-                const Dy2C k = dy2_consts();
-#pragma unroll
-                for (int m = 0; m < MO; ++m) {
-                    const int oc = fir_oct(lane) + 32 * m;
-                    if (oc >= NO) break;
-                    float dpq[2];
-                    dy2_dp(oc, dpq);
-                    float dy[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) dy[i] = dy2_at(k, vc[m][i], dpq[i >> 2], 8 * oc + i < T);
-                    if (EEGNET_LDSX_E != 5)
-                        lds_st_oct(drow + 8 * oc, oc, (floatx4){dy[0], dy[1], dy[2], dy[3]}, (floatx4){dy[4], dy[5], dy[6], dy[7]});
-                }
-            }
-            TRACE_PH(g, 4, 1, tph_);
-            wave_lds_fence();                              // dy rows complete, this wave's dp2 rows read
-        }
-        // this trial's x rows for the dws GEMM (the buffer was last read by the previous trial's
-        // GEMM); they land during the lag correlation / FIR^T, by the next barrier
-        if constexpr (XDMA)
+            // x DMA: this trial's x rows for the dws GEMM (the buffer was last read by the previous
+            // trial's GEMM); they land during the lag correlation / FIR^T, by the next barrier
             if (EEGNET_LDSX_E != 7)
                 x_dma_asm(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
-        TRACE_PH(g, 4, 2, tph_);
-        {
-            float tl[K1];
-            half_taps<K1, NTS>(tap, hr, tl);
-            // this wave's rows of the lag correlation (its own dy and s rows), then the transposed FIR
-            // e[P+s] = sum_m w1[K1-1-m] dypad[s+m], written over this wave's dy rows once every read
-            // of them is done.  Specialised shapes (one octet per lane, every row live) run both as one
-            // straight-line block, the lag-correlation MFMAs spread through the FIR^T's FMAs.
-            if constexpr (ONEOC) {
+            TRACE_PH(g, 4, 2, tph_);
+            {
+                float tl[K1];
+                half_taps<K1, NTS>(tap, hr, tl);
+                // lag correlation and FIR^T, fused: this wave's rows of the lag correlation (its own dy
+                // and s rows) and the transposed FIR e[P+s] = sum_m w1[K1-1-m] dypad[s+m], written over
+                // this wave's dy rows once every read of them is done, as one straight-line block, the
+                // lag-correlation MFMAs spread through the FIR^T's FMAs
                 constexpr int NT16C = (TT + 15) / 16, KQC = (NT16C + 3) / 4, NQ = RPW * KQC * NWT;
                 const int oc = fir_oct(lane);
                 float w[4 * G_::NW8];
@@ -1319,21 +1312,118 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                 wave_lds_fence();                          // every dy / s read of this wave is done
                 if (EEGNET_LDSX_E != 6)
                     lds_st_oct(erow + 8 * oc, oc, (floatx4){e[0], e[1], e[2], e[3]}, (floatx4){e[4], e[5], e[6], e[7]});
-                if constexpr (PIPEE) {                     // next trial's s rows of this wave
-                    // v(b + 1) is taken from its loads here, on every path to the GEMM phase: they went
-                    // out at the top of the trial, but the compiler's wait for them at a first use behind
-                    // the s DMAs (vmcnt is in order, and it counts no asm DMA) would wait for those too
+                // next s DMA: the next trial's s rows of this wave.
+                // v(b + 1) is taken from its loads here, on every path to the GEMM phase: they went
+                // out at the top of the trial, but the compiler's wait for them at a first use behind
+                // the s DMAs (vmcnt is in order, and it counts no asm DMA) would wait for those too
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(vpf[0][i]));
-                    if (bn < b1 && EEGNET_LDSX_E != 7) {
+                for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(vpf[0][i]));
+                if (bn < b1 && EEGNET_LDSX_E != 7) {
 #pragma unroll
-                        for (int r = 0; r < RPW; ++r) {
-                            const int o = RPW * wave + r;
-                            dma16(sg + ((size_t)bn * F2 + o) * s_pitch(T) + 4 * lane, Ss + o * RS + LP);
-                        }
+                    for (int r = 0; r < RPW; ++r) {
+                        const int o = RPW * wave + r;
+                        dma16(sg + ((size_t)bn * F2 + o) * s_pitch(T) + 4 * lane, Ss + o * RS + LP);
                     }
                 }
-            } else {
+            }
+            TRACE_PH(g, 4, 3, tph_);
+            // barrier: e rows, x rows complete; s rows, dp2 consumed (the x DMA is asm: explicit vmcnt).
+            // The RPW s DMAs of this wave may stay in flight
+            if (bn < b1) barrier_vm<RPW>();
+            else barrier_vm<0>();
+            TRACE_PH(g, 4, 4, tph_);
+            TRACE_PH(g, 4, 5, tph_);
+            // dws GEMM with the next trial's dy2 (-> registers) spread through it
+            if (gemm_on) {
+                const int c = ct * 16 + li;
+                const bool aon = li < F2, bon = c < C;
+                const int lo = 64 * (lk & 1) + 4 * (lk >> 1);
+                const float* arow = Dys + (aon ? li : 0) * RS + LP + lo;
+                const float* brow = Xb + (bon ? c : li) * RS + LP + lo;
+                // The wave's k-groups are a compile-time count here (NT16 = 16 over the 4 waves of a
+                // c-tile: 4), so every operand read issues before the first MFMA -- one LDS round
+                // trip instead of one per k-group -- and the one accumulator chain keeps its k order.
+                // dy2 of the next trial is spread through the chain (an element per two MFMAs): it
+                // fills the operand wait and the chain's dependent issue, and leaves dy in registers
+                // (other waves read e from the dy rows until the closing barrier).
+                const int to0 = 128 * (kg0 >> 3) + 8 * (kg0 & 7);      // kg0 = KGW part_: kg0 & 7 + j < 8
+                auto gemm = [&](auto ahead) {
+                    floatx4 a4[KGW], b4[KGW];
+#pragma unroll
+                    for (int j = 0; j < KGW; ++j) {
+                        if (EEGNET_LDSX_E == 4) {
+                            a4[j] = (floatx4){0.01f * (kg0 + j), 0.02f * li, 0.f, 1.f};
+                            b4[j] = (floatx4){0.03f * (kg0 + j), 0.01f * lk, 1.f, 0.f};
+                        } else {
+                            a4[j] = lds_ld4(arow + to0 + 8 * j);
+                            b4[j] = lds_ld4(brow + to0 + 8 * j);
+                        }
+                        if (!aon) a4[j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+                        if (!bon) b4[j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+                    }
+                    Dy2C k = {};
+                    float dpq[2] = {0.f, 0.f};
+                    if constexpr (decltype(ahead)::value) {
+                        k = dy2_consts();
+                        dy2_dp(fir_oct(lane), dpq);
+                    }
+#pragma unroll
+                    for (int n = 0; n < 4 * KGW; ++n) {
+                        xacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[n >> 2][n & 3], b4[n >> 2][n & 3], xacc, 0, 0, 0);
+                        if constexpr (decltype(ahead)::value)
+                            if (n & 1) dyh[n >> 1] = dy2_at(k, vpf[0][n >> 1], dpq[n >> 3], true);
+                    }
+                };
+                if (bn < b1) gemm(std::true_type{});
+                else gemm(std::false_type{});
+            }
+            // dp2 DMA two trials on: dy2(b + 1) has read dp2(b + 1)
+            if (bn + 1 < b1) dp2_ahead(bn + 1);
+            TRACE_PH(g, 4, 6, tph_);
+            // barrier: e, x rows consumed; s(b + 1) landed
+            if (bn + 1 < b1) barrier_vm<RPW>();
+            else barrier_vm<0>();
+            TRACE_PH(g, 4, 7, tph_);
+        }
+    } else if constexpr (DMA) {
+        // ---- DMA (22 x 257) ----
+        for (int b = b0; b < b1; ++b) {
+            const int bn = b + 1;
+            pace_prio(b - b0, b1 - b0);
+            float vc[MO][8];
+#pragma unroll
+            for (int m = 0; m < MO; ++m)
+#pragma unroll
+                for (int i = 0; i < 8; ++i) vc[m][i] = vpf[m][i];
+            TRACE_PH(g, 4, 0, tph_);
+            // dy2 from the prefetched v -> dy rows: this lane's octets; sums of dy and dy v
+            if (oh < F2) {
+                float* drow = Dys + oh * RS + LP;
+                const Dy2C k = dy2_consts();
+#pragma unroll
+                for (int m = 0; m < MO; ++m) {
+                    const int oc = fir_oct(lane) + 32 * m;
+                    if (oc >= NO) break;
+                    float dpq[2];
+                    dy2_dp(oc, dpq);
+                    float dy[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) dy[i] = dy2_at(k, vc[m][i], dpq[i >> 2], 8 * oc + i < T);
+                    if (EEGNET_LDSX_E != 5)
+                        lds_st_oct(drow + 8 * oc, oc, (floatx4){dy[0], dy[1], dy[2], dy[3]}, (floatx4){dy[4], dy[5], dy[6], dy[7]});
+                }
+            }
+            TRACE_PH(g, 4, 1, tph_);
+            wave_lds_fence();                              // dy rows complete, this wave's dp2 rows read
+            // x DMA: this trial's x rows for the dws GEMM (the buffer was last read by the previous
+            // trial's GEMM); they land during the lag correlation / FIR^T, by the next barrier
+            if (EEGNET_LDSX_E != 7)
+                x_dma_asm(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
+            TRACE_PH(g, 4, 2, tph_);
+            {
+                float tl[K1];
+                half_taps<K1, NTS>(tap, hr, tl);
+                // lag correlation (dy, s): this wave's rows, its own dy and s rows
                 const int KQ = (NT16 + 3) >> 2;
 #pragma unroll
                 for (int r = 0; r < RPW; ++r) {
@@ -1356,47 +1446,146 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                         }
                     }
                 }
-                if constexpr (EINPL) {                     // e over this wave's dy rows (MO octets per lane)
-                    float e[MO][8];
-                    if (oh < F2) {
-                        const float* dyr = Dys + oh * RS;
-                        constexpr bool TAIL1 = TT && (TT % 8 == 1) && (EEG_NO(TT) % 32 == 1);
+                // FIR^T (dy -> e, in place): e[P+s] = sum_m w1[K1-1-m] dypad[s+m] over this wave's dy rows
+                // (MO octets per lane), from registers once every read of the rows is done.  With the s
+                // rows staged by DMA (the next trial's land during the dws GEMM) e must not go to them
+                float e[MO][8];
+                if (oh < F2) {
+                    const float* dyr = Dys + oh * RS;
+                    constexpr bool TAIL1 = (TT % 8 == 1) && (EEG_NO(TT) % 32 == 1);
 #pragma unroll
-                        for (int m = 0; m < MO; ++m) {
-                            const int oc = min(fir_oct(lane) + 32 * m, NO - 1);
-                            float w[4 * G_::NW8];
-                            lds_window<G_::NW8>(dyr + 8 * oc, w);
+                    for (int m = 0; m < MO; ++m) {
+                        const int oc = min(fir_oct(lane) + 32 * m, NO - 1);
+                        float w[4 * G_::NW8];
+                        lds_window<G_::NW8>(dyr + 8 * oc, w);
 #pragma unroll
-                            for (int i = 0; i < 8; ++i) e[m][i] = 0.f;
-                            if (TAIL1 && m == MO - 1) {            // the last octet: sample T - 1 only
+                        for (int i = 0; i < 8; ++i) e[m][i] = 0.f;
+                        if (TAIL1 && m == MO - 1) {            // the last octet: sample T - 1 only
 #pragma unroll
-                                for (int k = 0; k < K1; ++k) e[m][0] = fmaf(tl[K1 - 1 - k], w[G_::OFFD + k], e[m][0]);
-                            } else {
+                            for (int k = 0; k < K1; ++k) e[m][0] = fmaf(tl[K1 - 1 - k], w[G_::OFFD + k], e[m][0]);
+                        } else {
 #pragma unroll
-                                for (int k = 0; k < K1; ++k)
+                            for (int k = 0; k < K1; ++k)
 #pragma unroll
-                                    for (int i = 0; i < 8; ++i)
-                                        e[m][i] = fmaf(tl[K1 - 1 - k], w[G_::OFFD + i + k], e[m][i]);
+                                for (int i = 0; i < 8; ++i)
+                                    e[m][i] = fmaf(tl[K1 - 1 - k], w[G_::OFFD + i + k], e[m][i]);
+                        }
+                    }
+                }
+                wave_lds_fence();                      // every dy / s read of this wave is done
+                if (oh < F2) {
+                    float* erow = Dys + oh * RS + LP;
+#pragma unroll
+                    for (int m = 0; m < MO; ++m) {
+                        const int oc = fir_oct(lane) + 32 * m;
+                        if (oc < NO) {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) e[m][i] = (8 * oc + i < T) ? e[m][i] : 0.f;
+                            lds_st_oct(erow + 8 * oc, oc, (floatx4){e[m][0], e[m][1], e[m][2], e[m][3]},
+                                       (floatx4){e[m][4], e[m][5], e[m][6], e[m][7]});
+                        }
+                    }
+                }
+            }
+            TRACE_PH(g, 4, 3, tph_);
+            // barrier: e rows, x rows complete; s rows, dp2 consumed (the x DMA is asm: explicit vmcnt)
+            barrier_vm<0>();
+            TRACE_PH(g, 4, 4, tph_);
+            if (bn < b1) {                                     // next trial's s / dp2 DMA and v loads
+                s_dma_asm(sg + (size_t)bn * F2 * s_pitch(T), F2, T, RS, LP, Ss, wave, lane);
+                flat_dma_asm(dp2g + (size_t)bn * ndp, ndp, DP, wave, lane);
+                asm volatile("" ::: "memory");                 // the v loads issue after the DMA (barrier_vm)
+                v_load<MO>(vg, bn, F2, NO, oh, lane, vpf);
+            }
+            TRACE_PH(g, 4, 5, tph_);
+            // dws GEMM (e, x) over the wave's k-groups.  22×257: the k-groups past the last whole
+            // 128-sample block (kg 16: t = 256 and the zero pad) keep the plain order t = 16 kg + 4 lk, the
+            // only 2-way group of the trial
+            if (gemm_on) {
+                const int c = ct * 16 + li;
+                const bool aon = li < F2, bon = c < C;
+                const int lo = 64 * (lk & 1) + 4 * (lk >> 1);
+                const float* arow = Dys + (aon ? li : 0) * RS + LP + lo;
+                const float* brow = Xb + (bon ? c : li) * RS + LP + lo;
+                for (int kg = kg0; kg < kg1; ++kg) {
+                    const int to = kg < KGP ? 128 * (kg >> 3) + 8 * (kg & 7) : 16 * kg + 4 * lk - lo;
+                    floatx4 a4, b4;
+                    if (EEGNET_LDSX_E == 4) {
+                        a4 = (floatx4){0.01f * kg, 0.02f * li, 0.f, 1.f};
+                        b4 = (floatx4){0.03f * kg, 0.01f * lk, 1.f, 0.f};
+                    } else {
+                        a4 = lds_ld4(arow + to);
+                        b4 = lds_ld4(brow + to);
+                    }
+                    if (!aon) a4 = (floatx4){0.f, 0.f, 0.f, 0.f};
+                    if (!bon) b4 = (floatx4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[e], b4[e], xacc, 0, 0, 0);
+                }
+            }
+            TRACE_PH(g, 4, 6, tph_);
+            // barrier: e, x rows consumed; next s rows and dp2 staged.  It waits for the DMA only: the
+            // 2 MO v loads issued after it stay in flight into the next trial
+            barrier_vm<2 * MO>();
+            TRACE_PH(g, 4, 7, tph_);
+        }
+    } else {
+        // ---- register-staged (the runtime shapes) ----
+        for (int b = b0; b < b1; ++b) {
+            const int bn = b + 1;
+            pace_prio(b - b0, b1 - b0);
+            float vc[MO][8];
+            v_load<MO>(vg, b, F2, NO, oh, lane, vc);           // v load
+            TRACE_PH(g, 4, 0, tph_);
+            // dy2 from v -> dy rows: this lane's octets; sums of dy and dy v
+            if (oh < F2) {
+                float* drow = Dys + oh * RS + LP;
+                const Dy2C k = dy2_consts();
+#pragma unroll
+                for (int m = 0; m < MO; ++m) {
+                    const int oc = fir_oct(lane) + 32 * m;
+                    if (oc >= NO) break;
+                    float dpq[2];
+                    dy2_dp(oc, dpq);
+                    float dy[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) dy[i] = dy2_at(k, vc[m][i], dpq[i >> 2], 8 * oc + i < T);
+                    if (EEGNET_LDSX_E != 5)
+                        lds_st_oct(drow + 8 * oc, oc, (floatx4){dy[0], dy[1], dy[2], dy[3]}, (floatx4){dy[4], dy[5], dy[6], dy[7]});
+                }
+            }
+            TRACE_PH(g, 4, 1, tph_);
+            wave_lds_fence();                              // dy rows complete, this wave's dp2 rows read
+            TRACE_PH(g, 4, 2, tph_);
+            {
+                float tl[K1];
+                half_taps<K1, NTS>(tap, hr, tl);
+                // lag correlation (dy, s): this wave's rows, its own dy and s rows
+                const int KQ = (NT16 + 3) >> 2;
+#pragma unroll
+                for (int r = 0; r < RPW; ++r) {
+                    const int o = RPW * wave + r;
+                    if (o < F2) {
+                        const float* dyr = Dys + o * RS + LP + li;
+                        const float* sr = Ss + o * RS + G_::OFF + li;
+                        for (int ks = 0; ks < KQ; ++ks) {
+                            const int a = 4 * ks + lk;
+                            const bool on = a < NT16;
+                            const int ac = on ? a : 0;
+                            float av = dyr[16 * ac];
+                            av = on ? av : 0.f;
+#pragma unroll
+                            for (int j = 0; j < NWT; ++j) {
+                                float bv = sr[16 * (ac + j)];
+                                bv = on ? bv : 0.f;
+                                cq[r][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, cq[r][j], 0, 0, 0);
                             }
                         }
                     }
-                    wave_lds_fence();                      // every dy / s read of this wave is done
-                    if (oh < F2) {
-                        float* erow = Dys + oh * RS + LP;
-#pragma unroll
-                        for (int m = 0; m < MO; ++m) {
-                            const int oc = fir_oct(lane) + 32 * m;
-                            if (oc < NO) {
-#pragma unroll
-                                for (int i = 0; i < 8; ++i) e[m][i] = (8 * oc + i < T) ? e[m][i] : 0.f;
-                                lds_st_oct(erow + 8 * oc, oc, (floatx4){e[m][0], e[m][1], e[m][2], e[m][3]},
-                                           (floatx4){e[m][4], e[m][5], e[m][6], e[m][7]});
-                            }
-                        }
-                    }
-                } else
-                // e -> this wave's s rows (the lag correlation above was their last reader; a wave's
-                // LDS reads and writes stay in order)
+                }
+                // FIR^T (dy -> e, to the s rows): e[P+s] = sum_m w1[K1-1-m] dypad[s+m] of this wave's dy
+                // rows -> its s rows (the lag correlation above was their last reader; a wave's LDS reads
+                // and writes stay in order)
                 if (oh < F2) {
                     const float* dyr = Dys + oh * RS;
                     float* erow = Ss + oh * RS + LP;
@@ -1416,114 +1605,28 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                     }
                 }
             }
-        }
-        TRACE_PH(g, 4, 3, tph_);
-        // the next trial's dp2 (register staging only; unconditional loads at clamped addresses)
-        if (!DPDMA && bn < b1) {
+            TRACE_PH(g, 4, 3, tph_);
+            if (bn < b1) {                                     // next dp2 loads, at clamped addresses
 #pragma unroll
-            for (int j = 0; j < NDP; ++j) pdp[j] = dp2g[(size_t)bn * ndp + min(tid + NTB * j, ndp - 1)];
-        }
-        // e rows, x rows complete; s rows, dp2 consumed (the x DMA is asm: explicit vmcnt)
-        if constexpr (PIPEE) {                             // the RPW s DMAs of this wave may stay in flight
-            if (bn < b1) barrier_vm<RPW>();
-            else barrier_vm<0>();
-        } else if constexpr (XDMA) barrier_vm<0>();
-        else __syncthreads();
-        TRACE_PH(g, 4, 4, tph_);
-        if (!PIPEE && bn < b1) {
-            if constexpr (XDMA) s_dma_asm(sg + (size_t)bn * F2 * s_pitch(T), F2, T, RS, LP, Ss, wave, lane);
-            else {                                         // registers over the dws GEMM only
+                for (int j = 0; j < NDP; ++j) pdp[j] = dp2g[(size_t)bn * ndp + min(tid + NTB * j, ndp - 1)];
+            }
+            __syncthreads();                               // e rows, x rows complete; s rows, dp2 consumed
+            TRACE_PH(g, 4, 4, tph_);
+            if (bn < b1) {                                     // next s / x loads: registers over the GEMM only
                 s_rows_load(bn);
                 x_prefetch<PF, NTB>(x + fold_row(perm, row0, bn) * (C * XP), C, T, pfx, tid);
+                asm volatile("" ::: "memory");                 // they issue here, ahead of the GEMM
             }
-            if constexpr (DPDMA) flat_dma_asm(dp2g + (size_t)bn * ndp, ndp, DP, wave, lane);
-            asm volatile("" ::: "memory");                 // the v loads issue after the DMA (barrier_vm)
-            if constexpr (VPF) v_load<MO>(vg, bn, F2, NO, oh, lane, vpf);
-        }
-        TRACE_PH(g, 4, 5, tph_);
-        // Xm[o][c] += sum_t e[o][t] x[c][t] on the matrix cores (16 e rows x 16 x rows of this wave's
-        // c-tile; the k order inside the wave's t range is permuted identically in A and B)
-        if (gemm_on) {
-            const int c = ct * 16 + li;
-            const bool aon = li < F2, bon = c < C;
-            if constexpr (TT != 0 && TT / 128 >= 2) {
-                // k-group kg of a 128-sample block: lane lk takes the float4 at t = 128 (kg >> 3) +
-                // 8 (kg & 7) + 64 (lk & 1) + 4 (lk >> 1), one ds_read_b128 per operand.  The 16-lane
-                // groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...) pair lk = 0 with 1 and 2 with 3, whose
-                // offsets now agree mod 64 floats (one bank row): a group is 16 distinct rows li, each on
-                // its own 4-bank slot (RS / 4 odd) -- conflict-free at one instruction per operand (the
-                // plain t = 16 kg + 4 lk order was 2-way; two ds_read_b64 per operand are conflict-free
-                // but cost more issue than the conflicts did)
-                // (a lane past the last channel reads -- and zeroes -- row li, not row 0: row 0 shares
-                // its 4-bank slot with row 16, which lane li = 0 of the second c-tile reads)
-                // 22×257: the k-groups past the last whole 128-sample block (kg 16: t = 256 and the
-                // zero pad) keep the plain order t = 16 kg + 4 lk, the only 2-way group of the trial
-                constexpr int KGP = 8 * (TT / 128);
-                const int lo = 64 * (lk & 1) + 4 * (lk >> 1);
-                const float* arow = Eb + (aon ? li : 0) * RS + LP + lo;
-                const float* brow = Xb + (bon ? c : li) * RS + LP + lo;
-                if constexpr (PIPEE) {
-                    // The wave's k-groups are a compile-time count here (NT16 = 16 over the 4 waves of a
-                    // c-tile: 4), so every operand read issues before the first MFMA -- one LDS round
-                    // trip instead of one per k-group -- and the one accumulator chain keeps its k order.
-                    // dy2 of the next trial is spread through the chain (an element per two MFMAs): it
-                    // fills the operand wait and the chain's dependent issue, and leaves dy in registers
-                    // (other waves read e from the dy rows until the closing barrier).
-                    constexpr int NCTC = (CC + 15) / 16, WPC = NWB / NCTC, KGW = ((TT + 15) / 16) / WPC;
-                    static_assert(WPC * NCTC == NWB && KGW * WPC == (TT + 15) / 16 && KGW * WPC <= KGP && 8 % KGW == 0 &&
-                                  4 * KGW == 2 * 8, "dws GEMM split of the pipelined shape");
-                    const int to0 = 128 * (kg0 >> 3) + 8 * (kg0 & 7);      // kg0 = KGW part_: kg0 & 7 + j < 8
-                    auto gemm = [&](auto ahead) {
-                        floatx4 a4[KGW], b4[KGW];
-#pragma unroll
-                        for (int j = 0; j < KGW; ++j) {
-                            if (EEGNET_LDSX_E == 4) {
-                                a4[j] = (floatx4){0.01f * (kg0 + j), 0.02f * li, 0.f, 1.f};
-                                b4[j] = (floatx4){0.03f * (kg0 + j), 0.01f * lk, 1.f, 0.f};
-                            } else {
-                                a4[j] = lds_ld4(arow + to0 + 8 * j);
-                                b4[j] = lds_ld4(brow + to0 + 8 * j);
-                            }
-                            if (!aon) a4[j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-                            if (!bon) b4[j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-                        }
-                        Dy2C k = {};
-                        float dpq[2] = {0.f, 0.f};
-                        if constexpr (decltype(ahead)::value) {
-                            k = dy2_consts();
-                            dy2_dp(fir_oct(lane), dpq);
-                        }
-#pragma unroll
-                        for (int n = 0; n < 4 * KGW; ++n) {
-                            xacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[n >> 2][n & 3], b4[n >> 2][n & 3], xacc, 0, 0, 0);
-                            if constexpr (decltype(ahead)::value)
-                                if (n & 1) dyh[n >> 1] = dy2_at(k, vpf[0][n >> 1], dpq[n >> 3], true);
-                        }
-                    };
-                    if (bn < b1) gemm(std::true_type{});
-                    else gemm(std::false_type{});
-                } else
-                for (int kg = kg0; kg < kg1; ++kg) {
-                    const int to = kg < KGP ? 128 * (kg >> 3) + 8 * (kg & 7) : 16 * kg + 4 * lk - lo;
-                    floatx4 a4, b4;
-                    if (EEGNET_LDSX_E == 4) {
-                        a4 = (floatx4){0.01f * kg, 0.02f * li, 0.f, 1.f};
-                        b4 = (floatx4){0.03f * kg, 0.01f * lk, 1.f, 0.f};
-                    } else {
-                        a4 = lds_ld4(arow + to);
-                        b4 = lds_ld4(brow + to);
-                    }
-                    if (!aon) a4 = (floatx4){0.f, 0.f, 0.f, 0.f};
-                    if (!bon) b4 = (floatx4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[e], b4[e], xacc, 0, 0, 0);
-                }
-            } else {
-                // operands by ds_read_b64: lane lk takes t = 16 kg + 2 lk + {0, 1} and 16 kg + 8 + 2 lk +
-                // {0, 1}.  A 32-lane group then reads 16 rows x 4 dwords = all 64 banks once (RS / 4 odd).
-                // The +8 halves go through an offset the compiler cannot see: two plain ds_read_b64 8
-                // floats apart merge into one ds_read2_b64, which banks mod 32 in 16-lane groups (2-way)
-                const float* arow = Eb + (aon ? li : 0) * RS + LP + 2 * lk;
+            TRACE_PH(g, 4, 5, tph_);
+            // dws GEMM (e is in the s rows), operands by ds_read_b64: lane lk takes t = 16 kg + 2 lk +
+            // {0, 1} and 16 kg + 8 + 2 lk + {0, 1}.  A 32-lane group then reads 16 rows x 4 dwords = all 64
+            // banks once (RS / 4 odd).  The +8 halves go through an offset the compiler cannot see: two
+            // plain ds_read_b64 8 floats apart merge into one ds_read2_b64, which banks mod 32 in 16-lane
+            // groups (2-way)
+            if (gemm_on) {
+                const int c = ct * 16 + li;
+                const bool aon = li < F2, bon = c < C;
+                const float* arow = Ss + (aon ? li : 0) * RS + LP + 2 * lk;
                 const float* brow = Xb + (bon ? c : (li < C ? li : 0)) * RS + LP + 2 * lk;
                 const int o8 = 8 + opaque0();
                 const float* arow8 = arow + o8;
@@ -1539,44 +1642,23 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
                     xacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[1], b1[1], xacc, 0, 0, 0);
                 }
             }
-        }
-        if (bn < b1) {
-            if constexpr (!DPDMA) {                        // next trial's dp2 rows: every reader is past
+            if (bn < b1) {                                     // dp2 stores: every reader is past
 #pragma unroll
                 for (int j = 0; j < NDP; ++j) {
                     const int i = tid + NTB * j;
                     if (i < ndp) DP[i] = pdp[j];
                 }
             }
-        }
-        if constexpr (PIPEE)
-            if (bn + 1 < b1) dp2_ahead(bn + 1);            // dy2(b + 1) has read dp2(b + 1)
-        TRACE_PH(g, 4, 6, tph_);
-        // (without DMA the next trial's x rows are stored right after the barrier: the next reader of
-        // the x buffer is that trial's dws GEMM, behind its first barrier)
-        // e, x rows consumed; next s rows and dp2 staged.  With both by DMA the barrier waits for the
-        // DMA only: the 2 MO v loads issued after it stay in flight into the next trial.
-        // The pipeline's vmcnt windows, from the wave's issue order over a trial b (b + 2 < b1):
-        //     end of trial b - 1:  dp2(b + 1) x RPW                 (b = b0: after the prologue's drain)
-        //     top of trial b:      v(b + 1) x 2 MO, x(b) x 2..3
-        //     after the FIR^T:     s(b + 1) x RPW                   mid barrier: vmcnt(RPW) -- all but s(b + 1)
-        //     after the GEMM:      dp2(b + 2) x RPW                 closing barrier: vmcnt(RPW) -- s(b + 1),
-        // read by this wave's lag correlation at the top of trial b + 1, has landed; dp2(b + 2) stays in
-        // flight until the next mid barrier.  The last trial's mid barrier and the last two trials' closing
-        // barriers have nothing behind what they wait for: vmcnt(0).
-        if constexpr (PIPEE) {
-            if (bn + 1 < b1) barrier_vm<RPW>();
-            else barrier_vm<0>();
-        }
-        else if constexpr (XDMA && DPDMA && VPF) barrier_vm<2 * MO>();
-        else if constexpr (XDMA || DPDMA) barrier_vm<0>();
-        else __syncthreads();
-        if constexpr (!XDMA)
+            TRACE_PH(g, 4, 6, tph_);
+            __syncthreads();                               // e, x rows consumed; next dp2 staged
+            // x / s stores, right after the barrier: the next reader of the x buffer is the next
+            // trial's dws GEMM, behind its first barrier
             if (bn < b1) {
                 x_store<PF, NTB>(pfx, C, T, RS, LP, Xb, tid);
                 s_rows_put();
             }
-        TRACE_PH(g, 4, 7, tph_);
+            TRACE_PH(g, 4, 7, tph_);
+        }
     }
     TRACE_LOOP(g, 4);
     tail_prio();

@@ -47,6 +47,8 @@ NARROW = [
     (3, 64, 8, 2, 64, 0.25, True),
     (4, 800, 8, 2, 32, 0.25, True),
     (22, 257, 6, 2, 32, 0.5, True),
+    # C in 33..48: three c-tiles in pass E's dws GEMM, two waves on each, waves 6 and 7 idle in it
+    (40, 64, 8, 2, 32, 0.25, True),
 ]
 WIDE = [
     (8, 64, 12, 2, 32, 0.5, False),     # F2 = 24: a partial o-chunk

@@ -1,8 +1,8 @@
-"""Pass E's one-trial-ahead pipeline (k_pass_e at the compile-time 22 x 256 EEGNet-8,2 shape, K1 = 32)
-at the ends of a workgroup's trial range.
+"""Pass E's look-ahead pipelines (k_pass_e at the compile-time EEGNet-8,2 shapes, K1 = 32) at the ends of a
+workgroup's trial range.
 
-The 22 x 256 kernel computes dy2 of trial b + 1 while the dws GEMM of trial b runs, and stages dp2 and v
-two trials ahead (eegnet_stream.hip pass_e_body, the PIPEE path).  What can go wrong sits at the range
+The 22 x 256 kernel (eegnet_stream.hip pass_e_body, the PIPE loop) computes dy2 of trial b + 1 while the
+dws GEMM of trial b runs, and stages dp2 and v two trials ahead.  What can go wrong sits at the range
 ends: a range of one trial (prologue and last trial are the same trial, nothing is looked ahead), of two
 (the look-ahead of the first trial is the last), of three (the first range with a trial that issues the
 loads of trial b + 2), an empty range beside them never (B >= the grid).  The cases therefore are, with
@@ -14,7 +14,11 @@ the library's answer, not this file's):
     B = G + G // 2     ranges of 1 and 2 trials in one launch
     B = 2 G + G // 2   ranges of 2 and 3 trials in one launch
 
-and each asserts its premise from launch_grids at that B (ranges of two and three trials need B > 2 G:
+The 22 x 257 kernel (the DMA loop) has a trial loop of its own: s, dp2 and v go one trial ahead and
+nothing further, so ranges of one and of two trials are the range ends that exist there.  Its cases are
+t257_one_trial (B = 1) and t257_ranges_1_2 (B = G + G // 2, G from launch_grids at that shape).
+
+Each case asserts its premise from launch_grids at that B (ranges of two and three trials need B > 2 G:
 1280 trials, 29 MB of x, on a 256-CU device -- the oracle step of that case is what takes its 6 s, once;
 the other cases take 0.4 to 4 s and every test that reuses a case's reference takes milliseconds).
 Per case ONE float64 oracle step
@@ -42,7 +46,10 @@ pytestmark = pytest.mark.gpu
 
 C, T, F1, D, K1, P = 22, 256, 8, 2, 32, 0.5
 SEED, OFFSET = 0x0E5E_ED01, 3
-CASES = ("one_trial", "one_each", "ranges_1_2", "ranges_2_3")
+# case -> (T, the trial counts of its ranges)
+CASES = {"one_trial": (256, "one_trial"), "one_each": (256, "one_each"), "ranges_1_2": (256, "ranges_1_2"),
+         "ranges_2_3": (256, "ranges_2_3"),
+         "t257_one_trial": (257, "one_trial"), "t257_ranges_1_2": (257, "ranges_1_2")}
 
 
 def _dev():
@@ -51,21 +58,22 @@ def _dev():
     return torch.device("cuda:0")
 
 
-def _model():
-    return random_model(C, T, F1=F1, D=D, K1=K1, p=P, seed=41)
+def _model(t):
+    return random_model(C, t, F1=F1, D=D, K1=K1, p=P, seed=41)
 
 
 def _batch(case):
     """B of the case and the trial counts its pass-E ranges hold, asserted from the library's grids."""
     from eegnetreplication_amd import ops
-    shape = _model().shape
+    t, kind = CASES[case]
+    shape = _model(t).shape
     G = ops.launch_grids(shape, 1 << 16)["E"]
     assert G >= 2
-    B = {"one_trial": 1, "one_each": G, "ranges_1_2": G + G // 2, "ranges_2_3": 2 * G + G // 2}[case]
+    B = {"one_trial": 1, "one_each": G, "ranges_1_2": G + G // 2, "ranges_2_3": 2 * G + G // 2}[kind]
     n = ops.launch_grids(shape, B)["E"]
     sizes = {(w + 1) * B // n - w * B // n for w in range(n)}       # eegnet_common.h trial_range
-    assert sizes == {"one_trial": {1}, "one_each": {1}, "ranges_1_2": {1, 2}, "ranges_2_3": {2, 3}}[case], (B, n, sizes)
-    assert n == (1 if case == "one_trial" else G)
+    assert sizes == {"one_trial": {1}, "one_each": {1}, "ranges_1_2": {1, 2}, "ranges_2_3": {2, 3}}[kind], (B, n, sizes)
+    assert n == (1 if kind == "one_trial" else G)
     return B
 
 
@@ -76,15 +84,15 @@ def _case(case):
     """Inputs and the float64 oracle step of a case, computed once and shared by its tests (read-only)."""
     if case not in _CASE:
         from oracle import numpy_ref as nr
-        B = _batch(case)
-        x_np, y_np = make_inputs(B, C, T, 7700 + B)
-        masks = device_masks(B, F1 * D, T, SEED, OFFSET, P)
-        params, bufs = state_np(_model())
+        B, t = _batch(case), CASES[case][0]
+        x_np, y_np = make_inputs(B, C, t, 7700 + B)
+        masks = device_masks(B, F1 * D, t, SEED, OFFSET, P)
+        params, bufs = state_np(_model(t))
         params = {k: v.astype(np.float64) for k, v in params.items()}
         ref = nr.train_step(params, bufs, x_np, y_np, nr.adam_init(params), p=P, masks=masks)
         for a in (x_np, y_np, *masks):
             a.setflags(write=False)
-        _CASE[case] = dict(B=B, x=x_np, y=y_np, masks=masks, ref=ref)
+        _CASE[case] = dict(B=B, T=t, x=x_np, y=y_np, masks=masks, ref=ref)
     return _CASE[case]
 
 
@@ -102,7 +110,7 @@ def _check_buffers(m, ref_nb, what):
 def _fused_step(c, dev):
     """One FusedTrainer step from the case's initial state: every output, on the host."""
     from eegnetreplication_amd import FusedTrainer
-    model = _model().to(dev).train()
+    model = _model(c["T"]).to(dev).train()
     model.next_dropout_key = lambda: (SEED, OFFSET)
     tr = FusedTrainer(model, lr=1e-3, eps=1e-7)
     logits = torch.empty((c["B"], 4), device=dev)
@@ -118,7 +126,7 @@ def _fused_step(c, dev):
 def test_fused_step_matches_oracle(case):
     dev = _dev()
     c = _case(case)
-    ref, what = c["ref"], f"fused 22x256 {case} B={c['B']}"
+    ref, what = c["ref"], f"fused 22x{c['T']} {case} B={c['B']}"
     out = _fused_step(c, dev)
     assert_close(out["logits"], ref["logits"], name=f"{what} logits")
     assert abs(out["loss"] - float(ref["loss"])) <= 1e-4 * max(1.0, abs(float(ref["loss"]))), what
@@ -131,8 +139,8 @@ def test_fused_step_matches_oracle(case):
 def test_module_step_matches_oracle(case):
     dev = _dev()
     c = _case(case)
-    ref, what = c["ref"], f"module 22x256 {case} B={c['B']}"
-    m = _model().to(dev).train()
+    ref, what = c["ref"], f"module 22x{c['T']} {case} B={c['B']}"
+    m = _model(c["T"]).to(dev).train()
     m.set_dropout_masks(torch.from_numpy(c["masks"][0]).to(dev), torch.from_numpy(c["masks"][1]).to(dev))
     y = torch.from_numpy(c["y"]).to(dev)
     logits = m(torch.from_numpy(c["x"]).to(dev))
