@@ -7,8 +7,8 @@ The compute runs in ``libeegnet_hip.so`` (hand-written gfx950 HIP kernels, C-ABI
 """
 
 from .model import EEGNet, FusedTrainer, evaluate_model, relevance_maps, saliency, train  # noqa: F401
-from .folds import FoldBatch, evaluate_folds  # noqa: F401
+from .folds import FoldBatch, FrozenFoldBatch, evaluate_folds  # noqa: F401
 from .ops import Shape  # noqa: F401
 
-__all__ = ["EEGNet", "FoldBatch", "FusedTrainer", "Shape", "evaluate_folds", "evaluate_model", "relevance_maps", "saliency",
-           "train"]
+__all__ = ["EEGNet", "FoldBatch", "FrozenFoldBatch", "FusedTrainer", "Shape", "evaluate_folds", "evaluate_model",
+           "relevance_maps", "saliency", "train"]

@@ -81,6 +81,10 @@ _SIGS = {
     "eegnet_train_step_folds": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64,
                                                ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
+    "eegnet_frozen_step_folds": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
+                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                                _vp]),
     "eegnet_eval_folds": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int,
                                          ctypes.c_int64, _vp]),
     "eegnet_eval_fold_bytes": (ctypes.c_size_t, []),

@@ -1,6 +1,7 @@
 // eegnet_frozen.hip -- frozen-BatchNorm fine-tuning: the fused forward + loss + backward + parameter
 // gradient kernel behind eegnet_frozen_step / eegnet_forward_frozen, and the reduction of its
-// per-workgroup partial rows.  Included by eegnet_kernels.hip (one translation unit).
+// per-workgroup partial rows; their fold-indexed instantiations (FOLD: blockIdx.y is the model) and the
+// fold-indexed Adam behind eegnet_frozen_step_folds.  Included by eegnet_kernels.hip (one translation unit).
 //
 // With the BatchNorm layers frozen (running statistics used and left untouched, dropout still on)
 // every trial is independent: none of the five batch-global reductions that split the train step into
@@ -78,14 +79,34 @@ __host__ __device__ inline FzCols fz_cols(const Geo& g) {
 // zeroing), a read-modify-write by the same lane afterwards
 __device__ __forceinline__ void fz_add(float* p, float v, bool first) { *p = first ? v : *p + v; }
 
-template <int K1, int CC, int TT, int FF, bool BWD>
+// The last argument of the frozen kernels: nothing for a single model; the call of a fold-indexed launch
+// (eegnet_frozen_step_folds), where blockIdx.y is the fold and its parameters, BN buffers, x, labels,
+// permutation and partial rows come from folds[blockIdx.y] (the pointer arguments are then unused).
+template <bool FOLD> struct FzFold {};
+template <> struct FzFold<true> { FoldCall fc; };
+
+template <int K1, int CC, int TT, int FF, bool BWD, bool FOLD = false>
 __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__ prm,
                                                 const float* __restrict__ bn, const float* __restrict__ x,
                                                 const float* __restrict__ dlog, const int64_t* __restrict__ lab,
                                                 const uint8_t* __restrict__ m2, const uint8_t* __restrict__ m3,
-                                                float* __restrict__ logits, float* part) {
+                                                float* __restrict__ logits, float* part, FzFold<FOLD> fold) {
     using G_ = KG<K1>;
     EEG_DIMS(g);
+    // fold launch: the batch is rows perm[row0 ...] (or row0 ...) of the fold's x / labels, seeded by the
+    // mean cross-entropy, its dropout key mix(seed, koff + *step) as a KEY_FROM_STEP single call's
+    // (row0 is folded into the pointers -- perm, or x and labels without one -- so one pointer stays live)
+    const int64_t* perm = nullptr;
+    unsigned key0 = 0u, key1 = 0u;
+    if constexpr (FOLD) {
+        const eegnet_fold f = fold_rec(fold.fc);
+        prm = f.params; bn = f.bn_buffers; part = (float*)f.ws;
+        dlog = nullptr; m2 = nullptr; m3 = nullptr; logits = nullptr;
+        perm = f.perm ? f.perm + fold.fc.row0 : nullptr;
+        x = f.perm ? f.x : f.x + (size_t)fold.fc.row0 * ((size_t)C * T);
+        lab = f.perm ? f.labels : f.labels + fold.fc.row0;
+        if (g.drop) { key0 = fold_drop_key(fold.fc, f, 0); key1 = fold_drop_key(fold.fc, f, 1); }
+    }
     constexpr int NCTM = CC ? (CC + 15) / 16 : 4;      // 16-channel tiles of the dws product (C <= 64)
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* const Xs = sm;
@@ -135,7 +156,7 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
         m3o = rm3[oo];
         b3 = prm[g.o_b3 + oo] - m3o * s3;
     }
-    const unsigned key0 = g.drop ? drop_key(g, 0) : 0u, key1 = g.drop ? drop_key(g, 1) : 0u;
+    if constexpr (!FOLD) { key0 = g.drop ? drop_key(g, 0) : 0u; key1 = g.drop ? drop_key(g, 1) : 0u; }
     const float invB = 1.f / (float)g.B;
     // sums kept in registers across this workgroup's trials
     float aG3 = 0.f, aB3 = 0.f, aG2 = 0.f, aB2 = 0.f, aDV = 0.f, aSU = 0.f, aLoss = 0.f;
@@ -147,8 +168,13 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
     float* const prow = BWD ? part + (size_t)blockIdx.x * fc.n : nullptr;
 
     const size_t nx = (size_t)C * T;
+    // trial b of the batch in x (and, with the same row index, in labels)
+    auto xrow = [&](auto b) {
+        if constexpr (FOLD) return x + (size_t)fold_row(perm, 0, (int)b) * nx;
+        else return x + (size_t)b * nx;
+    };
     float pf[PF];
-    if ((int)blockIdx.x < g.B) x_prefetch<PF>(x + (size_t)blockIdx.x * nx, C, T, pf, tid);
+    if ((int)blockIdx.x < g.B) x_prefetch<PF>(xrow(blockIdx.x), C, T, pf, tid);
     __syncthreads();
     x_store<PF>(pf, C, T, RS, LP, Xs, tid);
     __syncthreads();
@@ -157,7 +183,7 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
     for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
         const int bnx = b + gridDim.x;
         const bool first = b == (int)blockIdx.x;
-        if (bnx < g.B) x_prefetch<PF>(x + (size_t)bnx * nx, C, T, pf, tid);
+        if (bnx < g.B) x_prefetch<PF>(xrow(bnx), C, T, pf, tid);
         // ---------------- forward ----------------
         spatial_mfma<KS>(Xs, aw, Ss, C, F2, NT16, RS, LP, wave, lane);
         __syncthreads();                                   // s rows complete
@@ -240,7 +266,7 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
                 float l[NCLS];
 #pragma unroll
                 for (int n = 0; n < NCLS; ++n) l[n] = Lg[n];
-                const int cls = (int)lab[b];
+                const int cls = (int)lab[FOLD ? fold_row(perm, 0, b) : (long long)b];
                 const float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
                 float ex[NCLS], sum = 0.f, lc = 0.f;
 #pragma unroll
@@ -497,11 +523,19 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
 // parameter layout) and `loss`.  One output element per lane; the four waves of a workgroup take a
 // quarter of the rows each and their sums are added in row order, so the result is a function of the
 // partial rows alone.
+// FOLD: blockIdx.y is the fold, whose rows, parameters, BN buffers, `grads` and loss slot come from its record.
 constexpr int NTFR = 256, FR_OUT = 64;
+template <bool FOLD = false>
 __global__ __launch_bounds__(NTFR) void k_frozen_reduce(Geo g, const float* __restrict__ prm,
                                                         const float* __restrict__ bn,
                                                         const float* __restrict__ part, int nrows,
-                                                        float* __restrict__ grads, float* __restrict__ loss) {
+                                                        float* __restrict__ grads, float* __restrict__ loss,
+                                                        FzFold<FOLD> fold) {
+    if constexpr (FOLD) {
+        const eegnet_fold f = fold_rec(fold.fc);
+        prm = f.params; bn = f.bn_buffers; part = (const float*)f.ws; grads = f.grads;
+        loss = f.losses ? f.losses + fold.fc.slot : nullptr;
+    }
     __shared__ double sh[NTFR / FR_OUT][FR_OUT];
     const FzCols fc = fz_cols(g);
     const int tid = threadIdx.x, le = tid & (FR_OUT - 1), qd = tid / FR_OUT;
@@ -571,6 +605,28 @@ __global__ __launch_bounds__(NTFR) void k_frozen_reduce(Geo g, const float* __re
             grads[e] = v;
         }
     }
+}
+
+// k_adam for every fold of a fold-indexed frozen step (blockIdx.y the fold): the same element update with
+// the same scalars, so a fold's parameters and Adam state come out as eegnet_adam_step leaves them.  A
+// fold without Adam state keeps its parameters.  The step counters are advanced by k_step_inc_folds, a
+// launch of its own behind this one: every workgroup here reads its fold's counter.
+__global__ __launch_bounds__(256) void k_adam_folds(int64_t n, FoldCall fc) {
+    const eegnet_fold f = fold_rec(fc);
+    if (!f.adam_state) return;
+    const int s = *f.step + 1;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const float step_size = (float)((double)fc.lr / (1.0 - pow((double)fc.b1, (double)s)));
+        const float bc2s = (float)sqrt(1.0 - pow((double)fc.b2, (double)s));
+        adam_elem(f.params + i, f.grads[i], f.adam_state + i, f.adam_state + n + i, fc.b1, fc.b2, step_size, bc2s,
+                  fc.eps);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_step_inc_folds(FoldCall fc, int nfolds) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < nfolds && fc.folds[k].adam_state) *fc.folds[k].step += 1;
 }
 
 }  // namespace eeg

@@ -323,6 +323,7 @@ static void set_attrs_shape() {
     hipFuncSetAttribute((const void*)k_infer_dx<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_eval_folds<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
@@ -919,9 +920,12 @@ static int frozen_launch(const char* name, const Geo& g, bool bwd, const float* 
                          const uint8_t* m3, float* logits, float* part, hipStream_t s) {
     return dispatch_shape(g, [&](auto sh) {
         return launch(KID_NONE, name, bwd ? k_frozen<SHAPE_OF(sh), true> : k_frozen<SHAPE_OF(sh), false>, dim3(g.grid),
-                      dim3(NTH), g.ldsX * 4, s, g, params, bn, x, dlogits, labels, m2, m3, logits, part);
+                      dim3(NTH), g.ldsX * 4, s, g, params, bn, x, dlogits, labels, m2, m3, logits, part, FzFold<false>{});
     });
 }
+
+// workgroups of k_frozen_reduce: FR_OUT outputs each over the gradients and the loss
+static unsigned frozen_reduce_grid(const Geo& g) { return (unsigned)((g.nparam + 1 + FR_OUT - 1) / FR_OUT); }
 
 extern "C" {
 
@@ -969,13 +973,53 @@ int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_b
     float* part = (float*)ws;
     if (int r = frozen_launch("k_frozen", g, true, params, bn_buffers, x, dlogits, labels, mask2, mask3, logits, part, s))
         return r;
-    if (int r = launch(KID_NONE, "k_frozen_reduce", k_frozen_reduce, dim3((g.nparam + 1 + FR_OUT - 1) / FR_OUT),
-                       dim3(NTFR), 0, s, g, params, bn_buffers, part, g.grid, grads, loss)) return r;
+    if (int r = launch(KID_NONE, "k_frozen_reduce", k_frozen_reduce<false>, dim3(frozen_reduce_grid(g)),
+                       dim3(NTFR), 0, s, g, params, bn_buffers, part, g.grid, grads, loss, FzFold<false>{})) return r;
     if (!adam_state) return 0;
     // the Adam kernel of eegnet_adam_step behind the reduction; it advances the step counter last, after
     // k_frozen has read it for the dropout key (EEGNET_KEY_FROM_STEP)
     return eegnet_adam_step(g.nparam, params, grads, adam_state, adam_state + g.nparam, step, lr, beta1, beta2,
                             eps, stream);
+}
+
+// One frozen-BatchNorm iteration of nfolds models in four launches, whatever nfolds: k_frozen and
+// k_frozen_reduce with the fold in the grid's y, then Adam and the step counters.  The per-fold grid is
+// eegnet_frozen_step's for the same dims (g.grid, a function of B alone), so a fold's partial rows -- and
+// with them every bit of its result -- are those of that call on the fold alone.
+int eegnet_frozen_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
+                             int64_t slot, uint64_t offset, float lr, float beta1, float beta2, float eps,
+                             int flags, void* stream) {
+    Geo g;
+    if (int r = frozen_geo(dims, &g)) return r;
+    if (nfolds < 1 || nfolds > 65535) return fail(EEGNET_EINVAL, "nfolds must be in [1, 65535] (got %d)", nfolds);
+    if (!folds) return fail(EEGNET_EINVAL, "folds is NULL");
+    if (row0 < 0 || slot < 0) return fail(EEGNET_EINVAL, "row0 / slot must be >= 0");
+    if (flags & ~EEGNET_NO_CLAMP)
+        return fail(EEGNET_EINVAL, "frozen fold step: unknown flags 0x%x (the dropout keys always follow the "
+                    "folds' device steps)", flags & ~EEGNET_NO_CLAMP);
+    g.noclamp = (flags & EEGNET_NO_CLAMP) ? 1 : 0;
+    set_key(&g, 0, offset);                           // the keep threshold (keys come per fold)
+    ensure_attrs();
+    FoldCall fc;
+    memset(&fc, 0, sizeof(fc));
+    fc.folds = folds;
+    fc.row0 = row0; fc.slot = slot; fc.koff = offset;
+    fc.lr = lr; fc.b1 = beta1; fc.b2 = beta2; fc.eps = eps;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nf = (unsigned)nfolds;
+    const FzFold<true> fold{fc};
+    if (int r = dispatch_shape(g, [&](auto sh) {
+            return launch(KID_NONE, "k_frozen(folds)", k_frozen<SHAPE_OF(sh), true, true>, dim3(g.grid, nf), dim3(NTH),
+                          g.ldsX * 4, s, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, fold);
+        })) return r;
+    if (int r = launch(KID_NONE, "k_frozen_reduce(folds)", k_frozen_reduce<true>, dim3(frozen_reduce_grid(g), nf),
+                       dim3(NTFR), 0, s, g, nullptr, nullptr, nullptr, g.grid, nullptr, nullptr, fold)) return r;
+    // every reader of the step counters -- the dropout keys above, Adam's bias correction -- is in an
+    // earlier launch than their increment
+    if (int r = launch(KID_NONE, "k_adam_folds", k_adam_folds, dim3((unsigned)((g.nparam + 255) / 256), nf), dim3(256),
+                       0, s, (int64_t)g.nparam, fc)) return r;
+    return launch(KID_NONE, "k_step_inc_folds", k_step_inc_folds, dim3((nf + 255) / 256), dim3(256), 0, s, fc, nfolds);
 }
 
 }  // extern "C"

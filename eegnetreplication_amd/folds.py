@@ -15,6 +15,10 @@ counter-based per fold -- (fold seed, step counter) -- and a fold-indexed launch
 batch over workgroups by the batch size alone, so a fold's trajectory does not depend on how many
 other folds run beside it or on which rank it was dealt to (tests/test_gpu_folds.py checks
 bit-equality with the same fold run alone).
+
+``FrozenFoldBatch`` is the same for fine-tuning with frozen BatchNorm (``EEGNet.freeze_bn()``): the
+frozen step of every resident model in one fold-indexed call (eegnet_frozen_step_folds), each fold
+bit-identical to ``ops.frozen_step`` on it alone (tests/test_gpu_frozen_folds.py).
 """
 
 from __future__ import annotations
@@ -42,7 +46,62 @@ def _refuse_frozen(models):
     (EEGNet.freeze_bn) would silently train with batch statistics and move its running ones."""
     if any(getattr(m, "bn_frozen", False) for m in models):
         raise ValueError("FoldBatch does not support models with frozen BatchNorm (EEGNet.freeze_bn): "
-                         "fine-tune them with train() / FusedTrainer, or call freeze_bn(False)")
+                         "fine-tune them with FrozenFoldBatch, train() / FusedTrainer, or call freeze_bn(False)")
+
+
+def _require_frozen(models):
+    """Frozen fold batching runs the frozen-BatchNorm step only: a model in batch-statistics mode would
+    silently train without moving its running statistics."""
+    if not all(getattr(m, "bn_frozen", False) for m in models):
+        raise ValueError("FrozenFoldBatch needs every model's BatchNorm layers frozen (EEGNet.freeze_bn()): "
+                         "train batch-statistics models with FoldBatch")
+
+
+def _epoch_buffers(K, n, nsteps, dev):
+    """The per-epoch state of a fused fold launch.  The folds' permutations and loss slots are rows of
+    one [K, n] / [K, nsteps] buffer each: an epoch refreshes every permutation with ONE asynchronous
+    copy from a pinned host buffer (two, alternating: the host fills the next epoch's while the device
+    runs this one) and sums every fold's losses with one kernel."""
+    perm2 = torch.zeros((K, n), dtype=torch.int64, device=dev)
+    loss2 = torch.zeros((K, nsteps), dtype=torch.float32, device=dev)
+    return {"graph": None, "perm2": perm2, "perm": list(perm2.unbind(0)),
+            "loss2": loss2, "losses": list(loss2.unbind(0)),
+            "host": [torch.zeros((K, n), dtype=torch.int64).pin_memory() for _ in range(2)],
+            "copied": [None, None], "epoch": 0}
+
+
+def _stage_permutations(st, n, generators):
+    """This epoch's permutation of every fold into ``st["perm2"]``: one pinned-host copy."""
+    i = st["epoch"] & 1
+    st["epoch"] += 1
+    if st["copied"][i] is not None:     # this pinned buffer's copy (two epochs ago) has run
+        st["copied"][i].synchronize()
+    host = st["host"][i]
+    for k in range(host.shape[0]):
+        g = generators[k] if generators is not None else None
+        host[k].copy_(epoch_permutation(n, g) if g is not None else torch.arange(n))
+    st["perm2"].copy_(host, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    st["copied"][i] = ev
+
+
+def _run_epoch(st, steps, graphs):
+    """Replay the captured epoch, or enqueue it with ``steps()`` (and, with ``graphs``, capture it for
+    the next epochs); returns the folds' loss sums."""
+    if st["graph"] is not None:
+        st["graph"].replay()
+    else:
+        steps()
+        if graphs:                      # capture for the next epochs (tables / workspaces exist)
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                steps()
+            st["graph"] = gr
+            # the capture recorded without executing: run this epoch's work once more is NOT
+            # wanted -- the eager pass above already trained the epoch
+    return list(st["loss2"].sum(dim=1, dtype=torch.float64).unbind(0))
 
 
 class _At:
@@ -143,7 +202,78 @@ def evaluate_folds(models, sets, batch_size: int = 64, *, out=None):
     return (st["loss"], st["correct"]) if out is None else (lo, co)
 
 
-class FoldBatch:
+class _FoldStreams:
+    """What FoldBatch and FrozenFoldBatch share: the per-fold path of an epoch -- one HIP stream per
+    fold, each fold's epoch enqueued by the class's ``_steps`` and, with ``graphs``, captured as that
+    fold's hipGraph -- and the identity keys of what a captured epoch or a fold table baked in."""
+
+    def __len__(self):
+        return len(self.models)
+
+    def validate(self, sets, batch_size: int = 64):
+        """``evaluate_folds`` on this batch's models: per fold the validation loss (float64) and the
+        number of correct trials (int64) on ``sets[k] = (X_k, y_k)``, as device tensors, unsynchronised."""
+        return evaluate_folds(self.models, sets, batch_size)
+
+    def _fold_key(self, k, X, y, batch_size):
+        """What fold k's captured epoch baked in: its model / Adam buffers (re-created by ``.to()``,
+        ``.float()`` or a re-flatten), its X and y, the batch size and workspace."""
+        m, a = self.models[k], self.adam[k]
+        return (X.shape[0], batch_size, id(X), X.data_ptr(), id(y), y.data_ptr(),
+                m.flat_parameters().data_ptr(), m.flat_bn_buffers().data_ptr(),
+                m.flat_num_batches_tracked().data_ptr(), a.state.data_ptr(), a.grads.data_ptr(),
+                a.step.data_ptr())
+
+    def _fused_key(self, data, batch_size):
+        """Everything a fold table or the captured graph holds a raw device pointer to: each
+        model's flat parameters, BN buffers, counters, Adam state and gradients, and the identity
+        of every fold's X and y.  ``.to()`` / ``.cuda()`` / ``.float()`` or a re-flatten re-creates
+        the model buffers; a caller may pass new y tensors with the same X."""
+        ptrs = []
+        for m, a in zip(self.models, self.adam):
+            ptrs += [m.flat_parameters().data_ptr(), m.flat_bn_buffers().data_ptr(),
+                     m.flat_num_batches_tracked().data_ptr(), a.state.data_ptr(), a.grads.data_ptr(),
+                     a.step.data_ptr()]
+        return (data[0][0].shape[0], batch_size, tuple(ptrs),
+                tuple((id(X), X.data_ptr(), id(y), y.data_ptr()) for X, y in data))
+
+    def _epoch_streams(self, data, batch_size, generators):
+        cur = torch.cuda.current_stream()
+        sums = []
+        for k, (X, y) in enumerate(data):
+            n = X.shape[0]
+            nsteps = (n + batch_size - 1) // batch_size
+            g = generators[k] if generators is not None else None
+            perm = epoch_permutation(n, g) if g is not None else torch.arange(n)
+            s = self.streams[k]
+            s.wait_stream(cur)
+            st = self._graph[k]
+            with torch.cuda.stream(s):
+                key = self._fold_key(k, X, y, batch_size)
+                if st is not None and st.key == key:
+                    st.perm.copy_(perm, non_blocking=True)
+                    st.graph.replay()
+                    sums.append(st.losses.sum(dtype=torch.float64))
+                    continue
+                perm_d = perm.to(X.device)
+                losses = torch.zeros(nsteps, dtype=torch.float32, device=X.device)
+                self._steps(k, X, y, perm_d, losses, batch_size)
+                sums.append(losses.sum(dtype=torch.float64))
+                if self.graphs:                 # capture for the next epochs (workspaces exist now)
+                    gr = torch.cuda.CUDAGraph()
+                    sperm = perm_d.clone()
+                    slosses = torch.zeros_like(losses)
+                    with torch.cuda.graph(gr, stream=s):
+                        self._steps(k, X, y, sperm, slosses, batch_size)
+                    self._graph[k] = _FoldGraph(key, sperm, slosses, gr)
+        for s in self.streams:
+            cur.wait_stream(s)
+        for t in sums:
+            t.record_stream(cur)
+        return sums
+
+
+class FoldBatch(_FoldStreams):
     """k independent fold runs on one GPU, one HIP stream each.
 
     ``graphs=True`` captures each fold's epoch (batch gathers + fused steps) as a hipGraph after
@@ -185,14 +315,6 @@ class FoldBatch:
         self.xstats = bool(xstats)
         self._fz = None                     # fused-launch state: buffers, fold tables, graph
 
-    def __len__(self):
-        return len(self.models)
-
-    def validate(self, sets, batch_size: int = 64):
-        """``evaluate_folds`` on this batch's models: per fold the validation loss (float64) and the
-        number of correct trials (int64) on ``sets[k] = (X_k, y_k)``, as device tensors, unsynchronised."""
-        return evaluate_folds(self.models, sets, batch_size)
-
     def invalidate_x(self):
         """Recompute every fold's padded x copy and per-trial BN1 table from its X at the next epoch
         (for writes to X that PyTorch's version counter does not see: ``X.data``, DLPack, foreign
@@ -223,29 +345,7 @@ class FoldBatch:
                            losses[j:j + 1], lr=self.lr, betas=self.betas, eps=self.eps,
                            nbt=nbt, key_from_step=True)
 
-    def _fold_key(self, k, X, y, batch_size):
-        """What fold k's captured epoch baked in: its model / Adam buffers (re-created by ``.to()``,
-        ``.float()`` or a re-flatten), its X and y, the batch size and workspace."""
-        m, a = self.models[k], self.adam[k]
-        return (X.shape[0], batch_size, id(X), X.data_ptr(), id(y), y.data_ptr(),
-                m.flat_parameters().data_ptr(), m.flat_bn_buffers().data_ptr(),
-                m.flat_num_batches_tracked().data_ptr(), a.state.data_ptr(), a.grads.data_ptr(),
-                a.step.data_ptr())
-
     # -- fused launches: all folds in one grid --------------------------------------------------
-    def _fused_key(self, data, batch_size):
-        """Everything a fold table or the captured graph holds a raw device pointer to: each
-        model's flat parameters, BN buffers, counters, Adam state and gradients, and the identity
-        of every fold's X and y.  ``.to()`` / ``.cuda()`` / ``.float()`` or a re-flatten re-creates
-        the model buffers; a caller may pass new y tensors with the same X."""
-        ptrs = []
-        for m, a in zip(self.models, self.adam):
-            ptrs += [m.flat_parameters().data_ptr(), m.flat_bn_buffers().data_ptr(),
-                     m.flat_num_batches_tracked().data_ptr(), a.state.data_ptr(), a.grads.data_ptr(),
-                     a.step.data_ptr()]
-        return (data[0][0].shape[0], batch_size, tuple(ptrs),
-                tuple((id(X), X.data_ptr(), id(y), y.data_ptr()) for X, y in data))
-
     def _fused_state(self, data, batch_size):
         X0, _ = data[0]
         n = X0.shape[0]
@@ -256,19 +356,9 @@ class FoldBatch:
         dev = X0.device
         K = len(self.models)
         nsteps = (n + batch_size - 1) // batch_size
-        # any change: new tables, and the graph (which baked the old pointers in) is dropped.
-        # The folds' permutations and loss slots are rows of one [K, n] / [K, nsteps] buffer each:
-        # an epoch refreshes every permutation with ONE asynchronous copy from a pinned host buffer
-        # (two, alternating: the host fills the next epoch's while the device runs this one) and
-        # sums every fold's losses with one kernel.
-        perm2 = torch.zeros((K, n), dtype=torch.int64, device=dev)
-        loss2 = torch.zeros((K, nsteps), dtype=torch.float32, device=dev)
-        st = {"key": key, "src": [d for d in data], "graph": None,
-              "perm2": perm2, "perm": list(perm2.unbind(0)),
-              "loss2": loss2, "losses": list(loss2.unbind(0)),
-              "host": [torch.zeros((K, n), dtype=torch.int64).pin_memory() for _ in range(2)],
-              "copied": [None, None], "epoch": 0,
-              "tables": {}, "steps": []}
+        # any change: new tables, and the graph (which baked the old pointers in) is dropped
+        st = {"key": key, "src": [d for d in data], "tables": {}, "steps": [],
+              **_epoch_buffers(K, n, nsteps, dev)}
         # x rows at the pitch the kernels load fastest (22 x 257: 260 floats, 16-byte DMA units):
         # one padded copy per distinct X, kept for the life of this state and refreshed in place
         # (same storage: the tables and the graph stay valid) whenever X changes in place
@@ -331,31 +421,8 @@ class FoldBatch:
         n = data[0][0].shape[0]
         st = self._fused_state(data, batch_size)
         self._refresh_padded(st)
-        i = st["epoch"] & 1
-        st["epoch"] += 1
-        if st["copied"][i] is not None:     # this pinned buffer's copy (two epochs ago) has run
-            st["copied"][i].synchronize()
-        host = st["host"][i]
-        for k in range(len(self.models)):
-            g = generators[k] if generators is not None else None
-            host[k].copy_(epoch_permutation(n, g) if g is not None else torch.arange(n))
-        st["perm2"].copy_(host, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        st["copied"][i] = ev
-        if st["graph"] is not None:
-            st["graph"].replay()
-        else:
-            self._fused_steps(st, data)
-            if self.graphs:                 # capture for the next epochs (tables / workspaces exist)
-                torch.cuda.synchronize()
-                gr = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gr):
-                    self._fused_steps(st, data)
-                st["graph"] = gr
-                # the capture recorded without executing: run this epoch's work once more is NOT
-                # wanted -- the eager pass above already trained the epoch
-        return list(st["loss2"].sum(dim=1, dtype=torch.float64).unbind(0))
+        _stage_permutations(st, n, generators)
+        return _run_epoch(st, lambda: self._fused_steps(st, data), self.graphs)
 
     def epoch(self, data: list[tuple[torch.Tensor, torch.Tensor]], batch_size: int = 64,
               generators: list[torch.Generator] | None = None) -> list[torch.Tensor]:
@@ -369,36 +436,130 @@ class FoldBatch:
         _refuse_frozen(self.models)
         if self.fused and all(X.shape[0] == data[0][0].shape[0] for X, _ in data):
             return self._epoch_fused(data, batch_size, generators)
-        cur = torch.cuda.current_stream()
-        sums = []
-        for k, (X, y) in enumerate(data):
-            n = X.shape[0]
-            nsteps = (n + batch_size - 1) // batch_size
-            g = generators[k] if generators is not None else None
-            perm = epoch_permutation(n, g) if g is not None else torch.arange(n)
-            s = self.streams[k]
-            s.wait_stream(cur)
-            st = self._graph[k]
-            with torch.cuda.stream(s):
-                key = self._fold_key(k, X, y, batch_size)
-                if st is not None and st.key == key:
-                    st.perm.copy_(perm, non_blocking=True)
-                    st.graph.replay()
-                    sums.append(st.losses.sum(dtype=torch.float64))
-                    continue
-                perm_d = perm.to(X.device)
-                losses = torch.zeros(nsteps, dtype=torch.float32, device=X.device)
-                self._steps(k, X, y, perm_d, losses, batch_size)
-                sums.append(losses.sum(dtype=torch.float64))
-                if self.graphs:                 # capture for the next epochs (workspaces exist now)
-                    gr = torch.cuda.CUDAGraph()
-                    sperm = perm_d.clone()
-                    slosses = torch.zeros_like(losses)
-                    with torch.cuda.graph(gr, stream=s):
-                        self._steps(k, X, y, sperm, slosses, batch_size)
-                    self._graph[k] = _FoldGraph(key, sperm, slosses, gr)
-        for s in self.streams:
-            cur.wait_stream(s)
-        for t in sums:
-            t.record_stream(cur)
-        return sums
+        return self._epoch_streams(data, batch_size, generators)
+
+
+class FrozenFoldBatch(_FoldStreams):
+    """k independent frozen-BatchNorm fine-tuning runs on one GPU: ``FoldBatch`` for models whose
+    BatchNorm layers are frozen (``EEGNet.freeze_bn()``) -- fine-tuning a cross-subject model per
+    subject with k-fold validation, say.  Per fold the arithmetic is ``FusedTrainer.step``'s on a frozen
+    model (forward with the running statistics and dropout, mean CE, backward with the two clamps,
+    Adam); the running statistics and ``num_batches_tracked`` are never written.
+
+    The fused path advances every fold with four launches per batch (eegnet_frozen_step_folds: the
+    fold index in the grid, the epoch's shuffle read through per-fold permutations, x in place); the
+    per-fold path runs ``ops.frozen_step`` on the epoch's gathered rows, one HIP stream per fold.  Both
+    key the dropout masks by (fold seed, device Adam step) and split a fold's batch over workgroups by
+    the batch size alone, so they agree bit for bit, with and without ``graphs``."""
+
+    def __init__(self, models: list[EEGNet], seeds: list[int], lr=1e-3, betas=(0.9, 0.999),
+                 eps=1e-7, graphs=False, fused=None):
+        """``fused``: ``None`` picks the fused launches where they apply (one EEGNet shape with
+        F1*D <= 16 for every fold and, per epoch, the same number of trials) and
+        ``FUSED_MIN_FOLDS`` or more folds are resident.  ``graphs``: the first epoch runs eagerly,
+        the epoch is captured as a hipGraph and later epochs replay it."""
+        if len(models) != len(seeds) or not models:
+            raise ValueError("need one seed per model and at least one model")
+        _require_frozen(models)
+        dev = models[0].flat_parameters().device
+        if dev.type != "cuda":
+            raise RuntimeError("FrozenFoldBatch runs on a HIP device only")
+        self.models = models
+        self.seeds = [int(s) for s in seeds]
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.graphs = graphs
+        self.adam = [FusedAdamState(m) for m in models]
+        self.streams = [torch.cuda.Stream(device=dev) for _ in models]
+        self._ws: list[dict] = [{} for _ in models]
+        self._graph: list[_FoldGraph | None] = [None] * len(models)
+        same = all(m.shape == models[0].shape for m in models) and models[0].shape.F2 <= 16
+        if fused and not same:
+            raise ValueError("fused fold launches need the same EEGNet shape (F1*D <= 16) for every fold")
+        self.fused = (same and len(models) >= self.FUSED_MIN_FOLDS) if fused is None else bool(fused)
+        self._fz = None                     # fused-launch state: buffers, fold tables, graph
+
+    # fused=None takes the fused launches from this many folds on: profiles/frozen_folds_bench.json has
+    # them no slower than the per-fold path at every K measured (12, 36, 90), and nothing below 12
+    FUSED_MIN_FOLDS = 12
+
+    def _workspace(self, k, B):
+        ws = self._ws[k].get(B)
+        if ws is None:
+            ws = ops.new_frozen_workspace(self.models[k].shape, B, self.models[k].flat_parameters().device)
+            self._ws[k][B] = ws
+        return ws
+
+    def _steps(self, k, X, y, perm, losses, batch_size):
+        """Enqueue one epoch of fold k on the current stream, as FoldBatch._steps: the epoch's
+        shuffled copy of X gathered once, batch j its rows [jB, (j+1)B), its loss in losses[j]."""
+        m = self.models[k]
+        a = self.adam[k]
+        Xp, yp = X.index_select(0, perm), y.index_select(0, perm)
+        flat, bn, _ = m.flat_views()
+        for j, i in enumerate(range(0, perm.shape[0], batch_size)):
+            xb, yb = Xp[i:i + batch_size], yp[i:i + batch_size]
+            ops.frozen_step(m.shape, flat, bn, xb, self.seeds[k], 0, a.grads, self._workspace(k, xb.shape[0]),
+                            labels=yb, adam_state=a.state, step_i32=a.step, loss=losses[j:j + 1],
+                            lr=self.lr, betas=self.betas, eps=self.eps, key_from_step=True)
+
+    def _fused_state(self, data, batch_size):
+        X0, _ = data[0]
+        n = X0.shape[0]
+        key = self._fused_key(data, batch_size)
+        st = self._fz
+        if st is not None and st["key"] == key:
+            return st
+        dev = X0.device
+        shape = self.models[0].shape
+        for X, y in data:
+            if (X.device != dev or y.device != dev or X.dtype != torch.float32 or y.dtype != torch.int64
+                    or X.dim() != 3 or tuple(X.shape[1:]) != (shape.C, shape.T) or tuple(y.shape) != (n,)):
+                raise ValueError(f"every fold's data must be (X [n, {shape.C}, {shape.T}] float32, y [n] int64) on {dev}")
+            # the frozen kernels read x in place at pitch T: no padded copy, no BN1 table
+            if not X.is_contiguous() or not y.is_contiguous():
+                raise ValueError("FrozenFoldBatch takes contiguous X and y (call .contiguous() once, outside "
+                                 "the loop)")
+            if shape.T % 4 == 0 and X.data_ptr() % 16:
+                raise ValueError("X must be 16-byte aligned when T % 4 == 0")
+        K = len(self.models)
+        nsteps = (n + batch_size - 1) // batch_size
+        # any change: new tables, and the graph (which baked the old pointers in) is dropped
+        st = {"key": key, "src": [d for d in data], "tables": {}, "steps": [],
+              **_epoch_buffers(K, n, nsteps, dev)}
+        for j, i in enumerate(range(0, n, batch_size)):
+            B = min(batch_size, n - i)
+            st["steps"].append((i, j, B))
+            if B not in st["tables"]:       # one table per distinct batch size (the short last batch)
+                ents = []
+                for k, m in enumerate(self.models):
+                    a = self.adam[k]
+                    X, y = data[k]
+                    ents.append(dict(params=m.flat_parameters(), bn_buffers=m.flat_bn_buffers(), x=X, labels=y,
+                                     perm=st["perm"][k], grads=a.grads, adam_state=a.state, step=a.step,
+                                     losses=st["losses"][k], ws=self._workspace(k, B), seed=self.seeds[k]))
+                st["tables"][B] = ops.fold_table(ents, dev)
+        self._fz = st
+        return st
+
+    def _fused_steps(self, st):
+        shape = self.models[0].shape
+        K = len(self.models)
+        for i, j, B in st["steps"]:
+            ops.frozen_step_folds(shape, B, st["tables"][B], K, row0=i, slot=j, offset=0, lr=self.lr,
+                                  betas=self.betas, eps=self.eps)
+
+    def epoch(self, data: list[tuple[torch.Tensor, torch.Tensor]], batch_size: int = 64,
+              generators: list[torch.Generator] | None = None) -> list[torch.Tensor]:
+        """One fine-tuning epoch of every fold, as ``FoldBatch.epoch``: ``data[k] = (X_k [N_k,C,T]
+        fp32, y_k [N_k] int64)``, device-resident and contiguous; each fold shuffled by its own
+        generator as DataLoader(shuffle=True, generator=g) would and cut into batches of
+        ``batch_size`` with a short last batch.  Returns per-fold float64 device scalars: the sum of
+        the batch losses.  Nothing is synchronised."""
+        _require_frozen(self.models)
+        if len(data) != len(self.models):
+            raise ValueError("one (X, y) per fold")
+        if self.fused and all(X.shape[0] == data[0][0].shape[0] for X, _ in data):
+            st = self._fused_state(data, batch_size)
+            _stage_permutations(st, data[0][0].shape[0], generators)
+            return _run_epoch(st, lambda: self._fused_steps(st), self.graphs)
+        return self._epoch_streams(data, batch_size, generators)

@@ -391,6 +391,22 @@ def train_step_folds(shape: Shape, B: int, table: torch.Tensor, nfolds: int, row
         ctypes.c_float(eps), _stream()), "eegnet_train_step_folds")
 
 
+def frozen_step_folds(shape: Shape, B: int, table: torch.Tensor, nfolds: int, row0: int, slot: int,
+                      offset: int = 0, lr=1e-3, betas=(0.9, 0.999), eps=1e-7, p: float | None = None,
+                      clamp=True):
+    """eegnet_frozen_step_folds: one frozen-BatchNorm iteration (``frozen_step`` with labels and
+    ``key_from_step``) of ``nfolds`` independent models in four launches, the fold index in the grid's
+    y.  ``table`` from fold_table(); every fold trains on rows perm[row0 : row0 + B] (rows
+    [row0, row0 + B) without a perm) of its own contiguous x / labels, writes its loss to
+    losses[slot] and keeps its partial rows in its own ``ws`` (``new_frozen_workspace``); a fold
+    without ``adam_state`` stops after its gradients.  BN buffers are read only."""
+    _lib.check(_lib.load().eegnet_frozen_step_folds(
+        ctypes.byref(shape.dims(B, p)), ctypes.c_int(nfolds), _ptr(table), ctypes.c_int64(row0),
+        ctypes.c_int64(slot), ctypes.c_uint64(offset), ctypes.c_float(lr), ctypes.c_float(betas[0]),
+        ctypes.c_float(betas[1]), ctypes.c_float(eps), ctypes.c_int(0 if clamp else NO_CLAMP), _stream()),
+        "eegnet_frozen_step_folds")
+
+
 def eval_fold_table(entries, device) -> torch.Tensor:
     """Device array of ``eegnet_eval_fold`` entries (a uint8 tensor holding the packed structs).
     ``entries``: dicts with the eegnet_eval_fold pointer fields as tensors (or None) and ``n`` as an

@@ -8,6 +8,7 @@
  *   one hot-loop iteration    src/eegnet_repl/model.py:136-148 -> eegnet_train_step
  *   saliency / x.grad in .eval() (plain autograd on the nn.Module) -> eegnet_input_grad_eval
  *   the hot loop with bn.eval() on the three BatchNorm2d (fine-tuning) -> eegnet_frozen_step
+ *   that fine-tuning loop for many models at once (per-subject fine-tuning, k folds each) -> eegnet_frozen_step_folds
  *   the per-epoch validation loop src/eegnet_repl/model.py:151-172, many folds at once -> eegnet_eval_folds
  *
  * Conventions
@@ -238,6 +239,28 @@ typedef struct eegnet_fold {
 int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
                             int64_t slot, uint64_t offset, float lr, float beta1, float beta2, float eps,
                             void* stream);
+
+/* eegnet_frozen_step (forward with running statistics and dropout, mean CE, backward, all 12 gradients
+ * with both clamps, Adam) for `nfolds` independent models in four launches, whatever nfolds: the fold
+ * index is the grid's y dimension.  `folds` is a DEVICE array of eegnet_fold, the record of
+ * eegnet_train_step_folds unchanged.  Per fold: params (updated by Adam), bn_buffers (read, never
+ * written), x [N, C, T] contiguous (x_pitch 0 or T; 16-byte aligned when T % 4 == 0 -- the host never
+ * reads the table, so this is not checked), labels, perm (batch row r is row perm[row0 + r] of x /
+ * labels; NULL: row row0 + r), grads (written), adam_state and step (adam_state == NULL: the fold stops
+ * after its gradients and its step is not advanced), losses (the mean CE goes to losses[slot]; NULL: not
+ * written), ws (eegnet_frozen_workspace_bytes(dims) bytes of its own) and seed.  num_batches_tracked and
+ * xstat are ignored and never dereferenced.  The dropout key of a fold is mix(seed, offset + *step), read
+ * on the device (EEGNET_KEY_FROM_STEP semantics: a captured graph draws fresh masks at every replay);
+ * dims->p_drop is shared.  flags: 0 or EEGNET_NO_CLAMP; any other bit is EEGNET_EINVAL.
+ * The per-fold grid is eegnet_frozen_step's for the same dims -- a function of dims->B alone, never of
+ * nfolds -- so every output of a fold is bit-identical to eegnet_frozen_step with EEGNET_KEY_FROM_STEP,
+ * the same (seed, offset) and the batch's rows gathered, on that fold alone, wherever it stands in the
+ * table.  No atomics, no host synchronisation: capturable in a hipGraph.  1 <= nfolds <= 65535, row0 and
+ * slot >= 0, F1*D <= 16 only; the validation needs no GPU. */
+int eegnet_frozen_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds,
+                             int64_t row0, int64_t slot, uint64_t offset,
+                             float lr, float beta1, float beta2, float eps,
+                             int flags, void* stream);
 
 /* One model (fold) of a fold-indexed validation call.  Every pointer is a device pointer; an array of
  * these lives in DEVICE memory.  Nothing in it is written except through logits, ce, pred, loss and
