@@ -81,7 +81,7 @@ struct Geo {
     int gridA, gridE;    // passes A and E: gridS, or their own trials-per-workgroup in fold launches
     // LDS (floats)
     int ldsA, ldsB, ldsC, ldsD, ldsE, ldsI;
-    int ldsX;            // k_infer_dx (eegnet_input_grad.hip): x, s, ELU' plane, block-2 rows
+    int ldsX;            // k_infer_dx, k_frozen: the PLANE plan of trial_lds (eegnet_trial.hip)
     // optional timeline instrumentation (eegnet_trace_enable): [pass][workgroup][TR_SLOTS] stamps
     unsigned long long* trace;
     // F2 > 16 (eegnet_wide.hip): o-chunks of 16 rows, Gram electrode slice per chunk, block-2 rows

@@ -5,7 +5,7 @@
 //
 // The reference validates after every epoch (model.py:151-172): per DataLoader batch of `batch` trials
 // the mean CE, then running / len(loader), and the count of argmax == label.  In eval mode every trial
-// is independent, so k_eval_folds is k_infer's per-trial body (infer_trial, eegnet_passes.hip) with the
+// is independent, so k_eval_folds is k_infer's per-trial body (infer_trial, eegnet_trial.hip) with the
 // model taken from a device table of eegnet_eval_fold records.
 //
 // Grid: flat.  The (fold, trial) pairs are laid out as nfolds rows of max_n slots, pair p = fold * max_n
@@ -43,10 +43,8 @@ __device__ __forceinline__ eegnet_eval_fold eval_rec(const eegnet_eval_fold* fol
 
 // per-trial cross-entropy logsumexp(l) - l[y] (pass C's formulation) and argmax, lowest index on a tie
 __device__ __forceinline__ float ce_of_logits(const float (&l)[NCLS], int y) {
-    const float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
-    float se = 0.f;
-#pragma unroll
-    for (int n = 0; n < NCLS; ++n) se += expf(l[n] - mx);
+    float ex[NCLS], mx;
+    const float se = softmax4(l, ex, mx);
     const float lse = mx + logf(se);
     const float ly = y == 0 ? l[0] : y == 1 ? l[1] : y == 2 ? l[2] : l[3];
     return lse - ly;
@@ -64,7 +62,6 @@ template <int K1, int CC, int TT, int FF>
 __global__ __launch_bounds__(NTH) void k_eval_folds(Geo g, EvalCall ec) {
     EEG_DIMS(g);
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* const Xb0 = sm;
     float* const Lg = sm + (C + F2) * RS + 2 * F2 * RS2 + ((NF + 3) & ~3);     // the trial's logits
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -87,7 +84,7 @@ __global__ __launch_bounds__(NTH) void k_eval_folds(Geo g, EvalCall ec) {
         infer_ops_load<K1, CC, TT, FF, true>(g, prm, f.bn_buffers, wave, lane, w);
         x_prefetch<PF>(f.x + (size_t)t0 * nx, C, T, pf, tid);
         __syncthreads();                            // the pads are zero; the previous fold's readers are done
-        x_store<PF>(pf, C, T, RS, LP, Xb0, tid);
+        x_store<PF>(pf, C, T, RS, LP, sm, tid);
         __syncthreads();
         drain_prologue_loads();
         for (long long b = t0; b < t1; ++b) {

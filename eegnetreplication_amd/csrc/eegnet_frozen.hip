@@ -18,17 +18,14 @@
 //               dg1[g] += sum_{o in g} sum_t du (v - rm1 W_o)/sd1;  db1[g] += sum_{o in g} W_o sum_t du
 //               dw1[g,k] += a1 sum_{o in g} sum_t du[o,t] s[o,t+k-P]
 //               dws[o,c] += a1 sum_t ds'[o,t] x[c,t] + c1 sum_t du[o,t],   ds' = FIR^T_w1(du)
-// k_frozen has k_infer_dx's shape: 1024 threads, wave o owns row o of every [F2, T] plane, one workgroup
-// per trial in flight, trials strided over the grid, the next trial's x prefetched into registers.  LDS
-// (floats, make_geo's ldsX -- the same plan as k_infer_dx):
-//     Xs [C][RS]     x rows, kept until the dws product
-//     Ss [F2][RS]    s rows; after the dw1 correlation, ds'
-//     Vs [F2][RS]    v rows; then du
-//     D2s [F2][RS2]  d2 rows (left pad LP2)
-//     Qs [F2][RS2]   q rows (left pad LP2); then dr (all rows are read by every wave), then dq
-//     Hs [NF], Lg [4]
-// The pads of every padded row are zeroed once and never written, so nothing of a trial (a NaN
-// included) reaches the next one.
+// k_frozen is a whole-trial kernel: the layout, the weight operands and the forward and transposed pieces
+// are eegnet_trial.hip's, in its PLANE LDS plan (make_geo's ldsX); the BatchNorm fold is its own (the
+// backward needs 1/sd2 and 1/sd3 on their own, and s2 = g2 (1/sd2) rounds differently from g2/sd2).  Its rows:
+//     Xs   x rows, kept until the dws product
+//     Ss   s rows; after the dw1 correlation, ds'
+//     Ps   v rows; then du
+//     D2s  d2 rows
+//     Qs   q rows; then dr (all rows are read by every wave), then dq
 //
 // Gradient sums.  Everything a lane can keep cheaply stays in registers across the workgroup's trials
 // (the per-row BatchNorm sums, the classifier products, the dws MFMA accumulators); the three lag /
@@ -109,13 +106,14 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
     }
     constexpr int NCTM = CC ? (CC + 15) / 16 : 4;      // 16-channel tiles of the dws product (C <= 64)
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    const TrialLds L = trial_lds(C, F2, RS, RS2, NF, true);
     float* const Xs = sm;
-    float* const Ss = Xs + C * RS;
-    float* const Vs = Ss + F2 * RS;
-    float* const D2s = Vs + F2 * RS;
-    float* const Qs = D2s + F2 * RS2;
-    float* const Hs = Qs + F2 * RS2;
-    float* const Lg = Hs + ((NF + 3) & ~3);
+    float* const Ss = sm + L.Ss;
+    float* const Vs = sm + L.Ps;
+    float* const D2s = sm + L.D2s;
+    float* const Qs = sm + L.Qs;
+    float* const Hs = sm + L.Hs;
+    float* const Lg = sm + L.Lg;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lk = lane >> 4;
@@ -123,23 +121,15 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
     const float* rm2 = bn + 2 * g.F1;      const float* rv2 = rm2 + F2;
     const float* rm3 = rm2 + 2 * F2;       const float* rv3 = rm3 + F2;
 
-    for (int i = tid; i < (C + 2 * F2) * RS + 2 * F2 * RS2; i += NTH) sm[i] = 0.f;
-    float aw[KS];
-    load_ws_frag<KS>(prm + g.o_ws, C, F2, aw, lane);
+    for (int i = tid; i < L.Hs; i += NTH) sm[i] = 0.f;
+    InferOps<K1, KS> w;
+    infer_weights_load<K1, CC, TT, FF, false>(g, prm, wave, lane, w);
     const int o = wave;
     const bool row_on = o < F2;
     const int oo = row_on ? o : 0, gg = oo / g.D;
-    float tap[K1];
-#pragma unroll
-    for (int k = 0; k < K1; ++k) tap[k] = prm[g.o_w1 + gg * K1 + k];
     const float tapl = lane < K1 ? prm[g.o_w1 + gg * K1 + lane] : 0.f;     // tap `lane` (the ds' tail samples)
-    float w2[K2], w3[F2MAX];
-#pragma unroll
-    for (int k = 0; k < K2; ++k) w2[k] = prm[g.o_w2 + oo * K2 + k];
-#pragma unroll
-    for (int i = 0; i < F2MAX; ++i) w3[i] = i < F2 ? prm[g.o_W3 + oo * F2 + i] : 0.f;
     // frozen BN1 and BN2 folded: z2 = al v + be, (u - rm2)/sd2 = ax v + bx; BN3: z3 = s3 r + b3
-    float al, be, ax, bx, s2, s3, b3, i3, m3o;
+    float ax, bx, s2, i3, m3o;
     {
         const float a1 = prm[g.o_g1 + gg] / sqrtf(rv1[gg] + g.eps);
         const float c1 = prm[g.o_b1 + gg] - a1 * rm1[gg];
@@ -147,15 +137,16 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
         for (int c = 0; c < C; ++c) W += prm[g.o_ws + oo * C + c];
         const float i2 = 1.f / sqrtf(rv2[oo] + g.eps);
         s2 = prm[g.o_g2 + oo] * i2;
-        al = a1 * s2;
-        be = (c1 * W - rm2[oo]) * s2 + prm[g.o_b2 + oo];
+        w.al = a1 * s2;
+        w.be = (c1 * W - rm2[oo]) * s2 + prm[g.o_b2 + oo];
         ax = a1 * i2;
         bx = (c1 * W - rm2[oo]) * i2;
         i3 = 1.f / sqrtf(rv3[oo] + g.eps);
-        s3 = prm[g.o_g3 + oo] * i3;
+        w.s3 = prm[g.o_g3 + oo] * i3;
         m3o = rm3[oo];
-        b3 = prm[g.o_b3 + oo] - m3o * s3;
+        w.b3 = prm[g.o_b3 + oo] - m3o * w.s3;
     }
+    const float al = w.al, be = w.be, s3 = w.s3, b3 = w.b3;
     if constexpr (!FOLD) { key0 = g.drop ? drop_key(g, 0) : 0u; key1 = g.drop ? drop_key(g, 1) : 0u; }
     const float invB = 1.f / (float)g.B;
     // sums kept in registers across this workgroup's trials
@@ -174,87 +165,36 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
         else return x + (size_t)b * nx;
     };
     float pf[PF];
-    if ((int)blockIdx.x < g.B) x_prefetch<PF>(xrow(blockIdx.x), C, T, pf, tid);
-    __syncthreads();
-    x_store<PF>(pf, C, T, RS, LP, Xs, tid);
-    __syncthreads();
-    drain_prologue_loads();
+    // (xrow is evaluated before the guard, a perm[] load included: the host launches min(B, CUs) workgroups,
+    // so blockIdx.x < g.B in every launch and the guard only mirrors the other kernels')
+    trial_x_first<PF>((int)blockIdx.x < g.B, xrow(blockIdx.x), C, T, RS, LP, Xs, pf, tid);
 
     for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
         const int bnx = b + gridDim.x;
         const bool first = b == (int)blockIdx.x;
         if (bnx < g.B) x_prefetch<PF>(xrow(bnx), C, T, pf, tid);
         // ---------------- forward ----------------
-        spatial_mfma<KS>(Xs, aw, Ss, C, F2, NT16, RS, LP, wave, lane);
+        spatial_mfma<KS>(Xs, w.aw, Ss, C, F2, NT16, RS, LP, wave, lane);
         __syncthreads();                                   // s rows complete
-        if (row_on) {
-            const float* row = Ss + o * RS;
-            float* vrow = Vs + o * RS + LP;
-            float* drow = D2s + o * RS2 + LP2;
-            const unsigned i2 = ((unsigned)b * (unsigned)F2 + (unsigned)o) * (unsigned)T1;
-            for (int q = lane; q < T1; q += 64) {
-                float w[4 * G_::NW];
-                lds_window<G_::NW>(row + 4 * q, w);
-                float v[4];
-                fir4<K1, G_::OFF>(w, tap, v);
-                float pe = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) pe += elu_f(fmaf(al, v[i], be));
-                drow[q] = pe * 0.25f * keep_mul(g, m2, key0, i2 + (unsigned)q);
-                lds_st4(vrow + 4 * q, (floatx4){v[0], v[1], v[2], v[3]});
-            }
-            wave_lds_fence();
-            // block_2 depthwise: q[t] = sum_k w2[k] d2[t + k - 7]
-            const float* dr = D2s + o * RS2 + 1;
-            float* qrow = Qs + o * RS2 + LP2;
-#pragma unroll
-            for (int m = 0; m < MAXT1Q; ++m) {
-                const int t = lane + 64 * m;
-                if (t < T1) {
-                    float a = 0.f;
-#pragma unroll
-                    for (int k = 0; k < K2; ++k) a = fmaf(w2[k], dr[t + k], a);
-                    qrow[t] = a;
-                }
-            }
-        }
-        __syncthreads();                                   // q rows complete
-        float r[MAXT1Q];
-#pragma unroll
-        for (int m = 0; m < MAXT1Q; ++m) {
-            const int t = lane + 64 * m;
-            float a = 0.f;
-            if (row_on && t < T1) {
-#pragma unroll
-                for (int i = 0; i < F2MAX; ++i)
-                    if (i < F2) a = fmaf(w3[i], Qs[i * RS2 + LP2 + t], a);
-            }
-            r[m] = a;
-        }
+        const unsigned i2b = ((unsigned)b * (unsigned)F2 + (unsigned)oo) * (unsigned)T1;
         const unsigned i3b = ((unsigned)b * (unsigned)F2 + (unsigned)oo) * (unsigned)T2;
-#pragma unroll
-        for (int m = 0; m < MAXT1Q; ++m) {
-            const int t = lane + 64 * m;
-            const bool on = row_on && t < 8 * T2;
-            float e = on ? elu_f(fmaf(s3, r[m], b3)) : 0.f;
-            e += dpp<0xB1>(e);                 // 8-lane sums by DPP (xor 1, xor 2, half-row mirror)
-            e += dpp<0x4E>(e);
-            e += dpp<0x141>(e);
-            if (on && (t & 7) == 0)
-                Hs[o * T2 + (t >> 3)] = e * 0.125f * keep_mul(g, m3, key1, i3b + (unsigned)(t >> 3));
+        if (row_on) {
+            float* vrow = Vs + o * RS + LP;
+            temporal_row<K1>(Ss + o * RS, D2s + o * RS2 + LP2, T1, w.tap, lane, [&](int q, const float (&v)[4]) {
+                lds_st4(vrow + 4 * q, (floatx4){v[0], v[1], v[2], v[3]});
+                return elu_pool4(al, be, v) * keep_mul(g, m2, key0, i2b + (unsigned)q);
+            });
+            wave_lds_fence();
         }
+        float r[MAXT1Q];
+        block2_rows(F2, T1, RS2, D2s, Qs + LP2, w.w2, w.w3, row_on, o, lane, r);
+        pool8_head(T2, Hs, s3, b3, r, row_on, o, lane,
+                   [&](int j) { return keep_mul(g, m3, key1, i3b + (unsigned)j); });
         __syncthreads();                                   // h complete
-        if (wave < NCLS) {
-            const int n = wave;
-            float a = 0.f;
-            for (int i = lane; i < NF; i += 64) a = fmaf(prm[g.o_Wfc + n * NF + i], Hs[i], a);
-            a = wave_sum(a);
-            if (lane == 0) {
-                const float l = a + prm[g.o_bfc + n];
-                Lg[n] = l;
-                if (logits) logits[(size_t)b * NCLS + n] = l;
-            }
-        }
+        classifier(g, prm, Hs, NF, wave, lane, [&](int n, float l) {
+            Lg[n] = l;
+            if (logits) logits[(size_t)b * NCLS + n] = l;
+        });
         __syncthreads();                                   // logits of this trial in Lg
         if constexpr (BWD) {
             // ---------------- seed g = dL/dlogits of this trial ----------------
@@ -267,12 +207,13 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
 #pragma unroll
                 for (int n = 0; n < NCLS; ++n) l[n] = Lg[n];
                 const int cls = (int)lab[FOLD ? fold_row(perm, 0, b) : (long long)b];
-                const float mx = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
-                float ex[NCLS], sum = 0.f, lc = 0.f;
+                float ex[NCLS], mx, lc = 0.f;
+                const float sum = softmax4(l, ex, mx);
 #pragma unroll
-                for (int n = 0; n < NCLS; ++n) { ex[n] = expf(l[n] - mx); sum += ex[n]; lc = n == cls ? l[n] : lc; }
-#pragma unroll
-                for (int n = 0; n < NCLS; ++n) gs[n] = (ex[n] / sum - (n == cls ? 1.f : 0.f)) * invB;
+                for (int n = 0; n < NCLS; ++n) {
+                    gs[n] = (ex[n] / sum - (n == cls ? 1.f : 0.f)) * invB;
+                    lc = n == cls ? l[n] : lc;
+                }
                 aLoss += (logf(sum) + mx - lc) * invB;
             }
             // ---------------- backward ----------------
@@ -326,39 +267,13 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
                 }
             }
             __syncthreads();                               // the q rows are read: dr may land on them
-            if (row_on) {
-                float* qrow = Qs + o * RS2 + LP2;
-#pragma unroll
-                for (int m = 0; m < MAXT1Q; ++m) {
-                    const int t = lane + 64 * m;
-                    if (t < T1) qrow[t] = drv[m];
-                }
-            }
+            if (row_on) row_store(Qs + o * RS2 + LP2, T1, lane, drv);
             __syncthreads();                               // dr rows complete
             float dqv[MAXT1Q];
-            if (row_on) {
-                // dq[o,t] = sum_i W3[i,o] dr[i,t]
-                const float* w3c = prm + g.o_W3 + o;
-#pragma unroll
-                for (int m = 0; m < MAXT1Q; ++m) {
-                    const int t = lane + 64 * m;
-                    float a = 0.f;
-                    if (t < T1) {
-#pragma unroll
-                        for (int i = 0; i < F2MAX; ++i)
-                            if (i < F2) a = fmaf(w3c[i * F2], Qs[i * RS2 + LP2 + t], a);
-                    }
-                    dqv[m] = a;
-                }
-            }
+            if (row_on) w3t_rows(prm + g.o_W3 + o, F2, T1, RS2, Qs + LP2, lane, dqv);
             __syncthreads();                               // dr rows read: dq may land on them
             if (row_on) {
-                float* qrow = Qs + o * RS2 + LP2;
-#pragma unroll
-                for (int m = 0; m < MAXT1Q; ++m) {
-                    const int t = lane + 64 * m;
-                    if (t < T1) qrow[t] = dqv[m];
-                }
+                row_store(Qs + o * RS2 + LP2, T1, lane, dqv);
                 // dw2[o,k] += sum_t dq[o,t] d2[o,t+k-7]
                 const float* dr = D2s + o * RS2 + 1;
                 float cw[K2];
@@ -379,16 +294,12 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
                         fz_add(prow + fc.w2 + o * K2 + j + (K2 / 4) * lk, cw[j], first);
                 }
                 wave_lds_fence();
-                // dd2[q] = sum_k w2[k] dq[q - k + 7]; dz2[4q + i] = dd2[q]/4 m2/(1-p) ELU'(z2[4q + i]);
-                // BN2 / BN1 sums; du = s2 dz2 over the v row
+                // dz2[4q + i] = dd2[q]/4 m2/(1-p) ELU'(z2[4q + i]); BN2 / BN1 sums; du = s2 dz2 over the v row
                 const float* qb = Qs + o * RS2 + (LP2 + 7);
                 float* vrow = Vs + o * RS + LP;
-                const unsigned i2 = ((unsigned)b * (unsigned)F2 + (unsigned)o) * (unsigned)T1;
                 for (int q = lane; q < T1; q += 64) {
-                    float a = 0.f;
-#pragma unroll
-                    for (int k = 0; k < K2; ++k) a = fmaf(w2[k], qb[q - k], a);
-                    a *= 0.25f * keep_mul(g, m2, key0, i2 + (unsigned)q);
+                    float a = fir16_t(w.w2, qb, q);
+                    a *= 0.25f * keep_mul(g, m2, key0, i2b + (unsigned)q);
                     const floatx4 v = lds_ld4(vrow + 4 * q);
                     floatx4 du;
 #pragma unroll
@@ -414,13 +325,13 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
 #pragma unroll
                     for (int k = 0; k < 32; ++k) c1w[k] = 0.f;
                     for (int q = lane; q < T1; q += 64) {
-                        float w[4 * NWC];
-                        lds_window<NWC>(srow + 4 * q + kc, w);
+                        float win[4 * NWC];
+                        lds_window<NWC>(srow + 4 * q + kc, win);
                         const floatx4 du = lds_ld4(vrow + 4 * q);
 #pragma unroll
                         for (int k = 0; k < 32; ++k)
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) c1w[k] = fmaf(du[i], w[G_::OFF + i + k], c1w[k]);
+                            for (int i = 0; i < 4; ++i) c1w[k] = fmaf(du[i], win[G_::OFF + i + k], c1w[k]);
                     }
                     wave_reduce<32>(c1w);                  // lane 16 r: sum[j + 8 r] in c1w[j]
                     if (li == 0) {
@@ -429,33 +340,8 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
                     }
                 }
                 wave_lds_fence();
-                // ds'[t] = sum_k w1[k] du[t - k + P]: the forward FIR with the taps flipped, pads R | P, over
-                // the s row (its last reader was the correlation above)
-                const float* row = Vs + o * RS;
-                float* dsrow = Ss + o * RS + LP;
-                // one or two quads past a multiple of 64 are 64-lane dot products instead, lane k on tap k
-                // (as k_infer_dx)
-                const int NQF = (TQ >= 64 && (TQ & 63) != 0 && (TQ & 63) <= 2) ? (TQ & ~63) : TQ;
-                for (int q = lane; q < NQF; q += 64) {
-                    float w[4 * G_::NW];
-                    lds_window<G_::NW>(row + 4 * q, w);
-                    floatx4 d;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float a = 0.f;
-#pragma unroll
-                        for (int k = 0; k < K1; ++k) a = fmaf(tap[K1 - 1 - k], w[G_::OFFD + i + k], a);
-                        d[i] = 4 * q + i < T ? a : 0.f;
-                    }
-                    lds_st4(dsrow + 4 * q, d);
-                }
-                if (NQF < TQ) {
-                    for (int t = 4 * NQF; t < 4 * TQ; ++t) {
-                        float p = (lane < K1 && t < T) ? tapl * row[LP + t + G_::P - lane] : 0.f;
-                        p = wave_sum(p);
-                        if (lane == 0) dsrow[t] = p;
-                    }
-                }
+                // ds' = FIR^T_w1(du) over the s row (its last reader was the correlation above)
+                temporal_row_t<K1>(Vs + o * RS, Ss + o * RS + LP, T, TQ, w.tap, tapl, lane);
             }
             __syncthreads();                               // ds' rows complete
             // dws raw product sum_t ds'[o,t] x[c,t]: v_mfma_f32_16x16x4_f32, A = ds' tile (16 o x 4 t),

@@ -127,10 +127,11 @@ static int make_geo(const eegnet_dims* d, Geo* g, bool launch = true) {
     g->ldsD = std::max(dr_lds_floats(spec ? 1 : MAXT1Q), dr_tail_floats(spec));     // k_pass_dr
     g->ldsE = std::max((2 * g->F2 + g->C) * g->RS + rup(g->F2 * g->T1, 4) + 8 * g->F2,
                        NWB * 256 * (1 + (15 + g->K1 - 1) / 16 + 1));   // after the loop: dws, Cq tiles
-    g->ldsI = rows1 + g->F2 * g->RS + 2 * g->F2 * g->RS2 + nf4;
-    // k_infer_dx: x rows (then the dx staging rows), s rows (then al dz2), the ELU'(z2) plane (then ds),
-    // d2 / q rows (then dr / dq), h, the trial's logits; checked by eegnet_input_grad_eval alone
-    g->ldsX = rows1 + 2 * g->F2 * g->RS + 2 * g->F2 * g->RS2 + nf4 + 4;
+    // the whole-trial kernels carve trial_lds (eegnet_trial.hip): ldsI is its plain plan without the logits
+    // (k_infer; k_eval_folds launches with ldsI + NCLS), ldsX its PLANE plan with them (k_infer_dx, k_frozen;
+    // checked by check_lds_x alone)
+    g->ldsI = trial_lds(g->C, g->F2, g->RS, g->RS2, g->NF, false).Lg;
+    g->ldsX = trial_lds(g->C, g->F2, g->RS, g->RS2, g->NF, true).n;
     // the reduction tail and finalize reuse each pass kernel's LDS (doubles = 2 floats)
     auto tail = [](int ncols, int fin) { return 2 * (tail_s_doubles(ncols) + std::max(tail_scratch_doubles(ncols), fin)); };
     g->ldsA = std::max(g->ldsA, tail(g->nA, fin1_scratch_doubles(g->K1, g->F1, g->F2, g->C)));
@@ -749,6 +750,12 @@ int eegnet_forward_eval(const eegnet_dims* dims, const float* params, const floa
     });
 }
 
+// the PLANE plan of eegnet_trial.hip has to fit the LDS (k_infer_dx, k_frozen)
+static int check_lds_x(const Geo& g, const char* what) {
+    if (g.ldsX * 4 > LDS_MAX) return fail(EEGNET_EINVAL, "%s: dims need %d B of LDS (> %d)", what, g.ldsX * 4, LDS_MAX);
+    return 0;
+}
+
 int eegnet_input_grad_eval(const eegnet_dims* dims, const float* params, const float* bn_buffers,
                            const float* x, int seed_kind, const float* dlogits, const int64_t* targets,
                            float* dx, float* logits, void* stream) {
@@ -761,8 +768,7 @@ int eegnet_input_grad_eval(const eegnet_dims* dims, const float* params, const f
     if (int r = check_ptrs(x, "x", dx, "dx")) return r;
     if (seed_kind == EEGNET_SEED_DLOGITS && !dlogits) return fail(EEGNET_EINVAL, "EEGNET_SEED_DLOGITS needs dlogits");
     if (seed_kind == EEGNET_SEED_CE && !targets) return fail(EEGNET_EINVAL, "EEGNET_SEED_CE needs targets");
-    if (g.ldsX * 4 > LDS_MAX)
-        return fail(EEGNET_EINVAL, "input gradients: dims need %d B of LDS (> %d)", g.ldsX * 4, LDS_MAX);
+    if (int r = check_lds_x(g, "input gradients")) return r;
     if ((g.T & 3) == 0 && ((uintptr_t)x & 15)) return fail(EEGNET_EINVAL, "input gradients: x must be 16-byte aligned");
     // dx rows go out in 16-byte stores only when every row of it starts 16-byte aligned
     const int vec = (g.T & 3) == 0 && ((uintptr_t)dx & 15) == 0;
@@ -906,9 +912,7 @@ int eegnet_stage_sums(const eegnet_dims* dims, int pass, size_t* offset_bytes, i
 static int frozen_geo(const eegnet_dims* dims, Geo* g) {
     if (int r = make_geo_narrow(dims, g, "frozen BatchNorm")) return r;
     if (g->XP != g->T) return fail(EEGNET_EINVAL, "frozen BatchNorm takes x as [B][C][T] (x_pitch 0 or T)");
-    // k_frozen runs in k_infer_dx's LDS plan: x, s (then ds'), v (then du), the block-2 rows, h, logits
-    if (g->ldsX * 4 > LDS_MAX)
-        return fail(EEGNET_EINVAL, "frozen BatchNorm: dims need %d B of LDS (> %d)", g->ldsX * 4, LDS_MAX);
+    if (int r = check_lds_x(*g, "frozen BatchNorm")) return r;
     if (g->NF > NTH) return fail(EEGNET_EINVAL, "frozen BatchNorm: F2*(T/32) = %d > %d", g->NF, NTH);
     return 0;
 }

@@ -37,6 +37,7 @@
 #include "eegnet_common.h"
 #include "eegnet_finalize.hip"
 #include "eegnet_stream.hip"
+#include "eegnet_trial.hip"
 #include "eegnet_passes.hip"
 #include "eegnet_input_grad.hip"
 #include "eegnet_frozen.hip"

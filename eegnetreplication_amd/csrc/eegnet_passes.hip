@@ -1,45 +1,9 @@
 // eegnet_passes.hip -- the block-2-rate passes C and D of the restructured EEGNet train step and
 // the fused eval-mode forward.  Included by eegnet_kernels.hip (one translation unit); the passes
-// that stream x (A, B, E) are in eegnet_stream.hip.
-//
-// k_infer: workgroup = 1024 threads = 16 waves, one workgroup per CU, trials strided over the
-// grid.  Wave w owns output row o = w of every per-trial [F2, T] plane (F2 <= 16), so its FIR taps
-// are wave-uniform (SGPRs) and the FIR windows it reads are lane-contiguous float4s.
+// that stream x (A, B, E) are in eegnet_stream.hip.  k_infer is one of the whole-trial kernels: its
+// layout, operands and per-trial body (infer_trial) are eegnet_trial.hip's.
 
 namespace eeg {
-
-// block_2 forward of one trial in the row-per-wave layout: D2s (padded d2 rows) -> q (Qs) -> r.
-// Returns r[m] for t = lane + 64 m (m < MAXT1Q) of row o.  Contains one workgroup barrier.
-
-__device__ __forceinline__ void block2_rows(int F2, int T1, int RS2, const float* D2s, float* Qs,
-                                            const float (&w2)[K2], const float (&w3)[F2MAX], bool row_on,
-                                            int o, int lane, float (&r)[MAXT1Q]) {
-    if (row_on) {
-        const float* dr = D2s + o * RS2 + 1;
-#pragma unroll
-        for (int m = 0; m < MAXT1Q; ++m) {
-            const int t = lane + 64 * m;
-            if (t < T1) {
-                float a = 0.f;
-#pragma unroll
-                for (int k = 0; k < K2; ++k) a = fmaf(w2[k], dr[t + k], a);
-                Qs[o * RS2 + t] = a;
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < MAXT1Q; ++m) {
-        const int t = lane + 64 * m;
-        float a = 0.f;
-        if (row_on && t < T1) {
-#pragma unroll
-            for (int i = 0; i < F2MAX; ++i)
-                if (i < F2) a = fmaf(w3[i], Qs[i * RS2 + t], a);
-        }
-        r[m] = a;
-    }
-}
 
 // ================================================================================================
 // Block-2-rate pass C: one trial per wave.  Lane t holds pooled sample t (+64 m) of all F2 rows, so
@@ -775,118 +739,8 @@ __global__ __launch_bounds__(NTB, TT ? WPEB : 2) void k_pass_dr(Geo g, const flo
 // ================================================================================================
 // Eval-mode forward (model.py:91-99 with .eval()): one fused kernel, BN running statistics folded
 // into per-row affine maps, no dropout.  The per-model operands (infer_ops_load) and the per-trial body
-// (infer_trial) are shared with the fold-indexed validation kernel (eegnet_eval_folds.hip).
+// (infer_trial) are eegnet_trial.hip's, shared with the other whole-trial kernels.
 // ================================================================================================
-// what a workgroup keeps in registers of one model: the spatial MFMA fragment, and of wave o's row the
-// temporal taps, block-2 weights and the folded BatchNorm maps
-template <int K1, int KS_>
-struct InferOps {
-    float aw[KS_];
-    float tap[K1];
-    float w2[K2], w3[F2MAX];
-    float al, be, s3, b3;
-};
-
-// a wave-uniform parameter load: plain (kernel-argument pointers: the compiler proves it scalar), or
-// SC = true through the constant address space (ldc) for pointers that come from a fold record and
-// loads that follow the kernel's own stores, which would otherwise land in one VGPR per value
-template <bool SC>
-__device__ __forceinline__ float ld_w(const float* p) {
-    if constexpr (SC) return ldc(p);
-    else return *p;
-}
-
-template <int K1, int CC, int TT, int FF, bool SC, int KS_>
-__device__ __forceinline__ void infer_ops_load(const Geo& g, const float* __restrict__ prm,
-                                               const float* __restrict__ bn, int wave, int lane,
-                                               InferOps<K1, KS_>& w) {
-    EEG_DIMS(g);
-    static_assert(KS_ == KS, "InferOps: k-steps of the spatial fragment");
-    const float* rm1 = bn;                 const float* rv1 = bn + g.F1;
-    const float* rm2 = bn + 2 * g.F1;      const float* rv2 = rm2 + F2;
-    const float* rm3 = rm2 + 2 * F2;     const float* rv3 = rm3 + F2;
-    load_ws_frag<KS>(prm + g.o_ws, C, F2, w.aw, lane);
-    const int o = wave;
-    const int oo = o < F2 ? o : 0, gg = oo / g.D;
-#pragma unroll
-    for (int k = 0; k < K1; ++k) w.tap[k] = ld_w<SC>(prm + (g.o_w1 + gg * K1 + k));
-#pragma unroll
-    for (int k = 0; k < K2; ++k) w.w2[k] = ld_w<SC>(prm + (g.o_w2 + oo * K2 + k));
-#pragma unroll
-    for (int i = 0; i < F2MAX; ++i) w.w3[i] = i < F2 ? ld_w<SC>(prm + (g.o_W3 + oo * F2 + i)) : 0.f;
-    // eval BN1 (model.py:32) and BN2 (model.py:47) folded: z2 = al * v + be; BN3: z3 = s3 r + b3
-    {
-        const float a1 = ld_w<SC>(prm + (g.o_g1 + gg)) / sqrtf(ld_w<SC>(rv1 + gg) + g.eps);
-        const float c1 = ld_w<SC>(prm + (g.o_b1 + gg)) - a1 * ld_w<SC>(rm1 + gg);
-        float W = 0.f;
-        for (int c = 0; c < C; ++c) W += ld_w<SC>(prm + (g.o_ws + oo * C + c));
-        const float s2 = ld_w<SC>(prm + (g.o_g2 + oo)) / sqrtf(ld_w<SC>(rv2 + oo) + g.eps);
-        w.al = a1 * s2;
-        w.be = (c1 * W - ld_w<SC>(rm2 + oo)) * s2 + ld_w<SC>(prm + (g.o_b2 + oo));
-        w.s3 = ld_w<SC>(prm + (g.o_g3 + oo)) / sqrtf(ld_w<SC>(rv3 + oo) + g.eps);
-        w.b3 = ld_w<SC>(prm + (g.o_b3 + oo)) - ld_w<SC>(rm3 + oo) * w.s3;
-    }
-}
-
-// One trial whose x rows are in the workgroup's x buffer: its four logits go to out(n, logit), called by
-// lane 0 of wave n.  xn (wave-uniform, NULL: none) is the next trial: its x is fetched into pf at the top
-// and stored over the x rows once their last reader, the spatial GEMM, is done.  Ends in a barrier.
-template <int K1, int CC, int TT, int FF, int KS_, int PF_, typename Out>
-__device__ __forceinline__ void infer_trial(const Geo& g, const float* __restrict__ prm,
-                                            const InferOps<K1, KS_>& w, float* sm,
-                                            const float* __restrict__ xn, float (&pf)[PF_], int tid, int wave,
-                                            int lane, Out&& out) {
-    using G_ = KG<K1>;
-    EEG_DIMS(g);
-    static_assert(KS_ == KS && PF_ == PF, "infer_trial: fragment / prefetch sizes of this shape");
-    float* const Xb0 = sm;             // one x buffer: the next trial lands after its last reader
-    float* Ss = sm + C * RS;
-    float* D2s = Ss + F2 * RS;
-    float* Qs = D2s + F2 * RS2;
-    float* Hs = Qs + F2 * RS2;
-    const int o = wave;
-    const bool row_on = o < F2;
-    if (xn) x_prefetch<PF>(xn, C, T, pf, tid);
-    spatial_mfma<KS>(Xb0, w.aw, Ss, C, F2, NT16, RS, LP, wave, lane);
-    __syncthreads();
-    if (row_on) {
-        const float* row = Ss + o * RS;
-        float* drow = D2s + o * RS2 + LP2;
-        for (int q = lane; q < T1; q += 64) {
-            float win[4 * G_::NW];
-            lds_window<G_::NW>(row + 4 * q, win);
-            float v[4];
-            fir4<K1, G_::OFF>(win, w.tap, v);
-            float pe = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pe += elu_f(fmaf(w.al, v[i], w.be));
-            drow[q] = pe * 0.25f;
-        }
-    }
-    if (xn) x_store<PF>(pf, C, T, RS, LP, Xb0, tid);
-    __syncthreads();
-    float r[MAXT1Q];
-    block2_rows(F2, T1, RS2, D2s, Qs, w.w2, w.w3, row_on, o, lane, r);
-#pragma unroll
-    for (int m = 0; m < MAXT1Q; ++m) {
-        const int t = lane + 64 * m;
-        float e = (row_on && t < 8 * T2) ? elu_f(fmaf(w.s3, r[m], w.b3)) : 0.f;
-        e += dpp<0xB1>(e);                 // 8-lane sums by DPP (xor 1, xor 2, half-row mirror)
-        e += dpp<0x4E>(e);
-        e += dpp<0x141>(e);
-        if (row_on && (t & 7) == 0 && t < 8 * T2) Hs[o * T2 + (t >> 3)] = e * 0.125f;
-    }
-    __syncthreads();
-    if (wave < NCLS) {
-        const int n = wave;
-        float a = 0.f;
-        for (int i = lane; i < NF; i += 64) a = fmaf(prm[g.o_Wfc + n * NF + i], Hs[i], a);
-        a = wave_sum(a);
-        if (lane == 0) out(n, a + prm[g.o_bfc + n]);
-    }
-    __syncthreads();
-}
-
 template <int K1, int CC, int TT, int FF>
 __global__ __launch_bounds__(NTH) void k_infer(Geo g, const float* __restrict__ prm,
                                                const float* __restrict__ bn,
@@ -894,7 +748,6 @@ __global__ __launch_bounds__(NTH) void k_infer(Geo g, const float* __restrict__ 
     EEG_DIMS(g);
     TRACE(g, 5, TR_ENTRY);
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* const Xb0 = sm;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
@@ -904,7 +757,7 @@ __global__ __launch_bounds__(NTH) void k_infer(Geo g, const float* __restrict__ 
     float pf[PF];
     if ((int)blockIdx.x < g.B) x_prefetch<PF>(x + (size_t)blockIdx.x * C * T, C, T, pf, tid);
     __syncthreads();
-    x_store<PF>(pf, C, T, RS, LP, Xb0, tid);
+    x_store<PF>(pf, C, T, RS, LP, sm, tid);
     __syncthreads();
 
     TRACE(g, 5, TR_PRO);

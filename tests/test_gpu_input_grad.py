@@ -79,6 +79,18 @@ def test_dx_matches_float64_oracle(C, T, B, F1, D, K1):
     _check_parity(model, state, x, y, dl, f"EEGNet-{F1},{D} K1={K1} {C}x{T} B={B}")
 
 
+@pytest.mark.parametrize("C,T,B,F1,D,K1", [(22, 257, 5, 8, 2, 32), (5, 96, 3, 4, 1, 32), (22, 257, 2, 8, 2, 64)])
+def test_dx_logits_equal_the_eval_forward(C, T, B, F1, D, K1):
+    """k_infer_dx's forward half is k_infer's arithmetic on k_infer's operands: the logits input_grad_eval
+    returns are forward_eval's, bit for bit."""
+    from eegnetreplication_amd import ops
+    model, _, x, y, _ = _case(C, T, B, F1, D, K1)
+    xd = torch.from_numpy(np.ascontiguousarray(x)).to(_dev())
+    want = ops.forward_eval(model.shape, model.flat_parameters(), model.flat_bn_buffers(), xd)
+    _, lg = _run(model, xd, "ce", targets=y)
+    assert torch.equal(lg, want)
+
+
 def test_dx_with_more_trials_than_the_launch_grid():
     """8 x 64 with B = 2 * grid + 3 (the host launches min(B, CUs) workgroups): the strided trial loop
     and the reuse of the x rows (as dx staging, then for the prefetched next trial) run."""
