@@ -65,6 +65,11 @@ _SIGS = {
                                           ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_float,
                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp,
                                           ctypes.c_int]),
+    "eegnet_trainable_offset": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "eegnet_frozen_step_from": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_float,
+                                               ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp,
+                                               ctypes.c_int, ctypes.c_int]),
     "eegnet_forward_eval_bf16": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, _vp, _vp]),
     "eegnet_adam_step": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
@@ -85,6 +90,10 @@ _SIGS = {
                                                 ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
                                                 ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int,
                                                 _vp]),
+    "eegnet_frozen_step_folds_from": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64,
+                                                     ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
+                                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                                     _vp, ctypes.c_int]),
     "eegnet_eval_folds": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int,
                                          ctypes.c_int64, _vp]),
     "eegnet_eval_fold_bytes": (ctypes.c_size_t, []),

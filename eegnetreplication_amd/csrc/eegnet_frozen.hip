@@ -76,13 +76,50 @@ __host__ __device__ inline FzCols fz_cols(const Geo& g) {
 // zeroing), a read-modify-write by the same lane afterwards
 __device__ __forceinline__ void fz_add(float* p, float v, bool first) { *p = first ? v : *p + v; }
 
+// db2 += dz2 = a e of a cut stage, rounded as the stage-0 instantiation of the same shape rounds its
+// `aB2 += dz2`: the compiler contracts that statement into fma(a, e, aB2) in the run-time-shape
+// instantiations and keeps the rounded product and a plain add in the compile-time-shape ones (SPEC), where
+// the sum is scheduled behind the du store.  Stage 0 must stay the code it was, so the cut stages spell
+// out either form; tests/test_gpu_partial_finetune.py compares the bits with stage 0 for both kinds.
+template <bool SPEC>
+__device__ __forceinline__ float fz_b2_add(float acc, float a, float e) {
+    if constexpr (SPEC) {
+#pragma clang fp contract(off)
+        const float dz2 = a * e;
+        return acc + dz2;
+    } else {
+        return fmaf(a, e, acc);
+    }
+}
+
 // The last argument of the frozen kernels: nothing for a single model; the call of a fold-indexed launch
 // (eegnet_frozen_step_folds), where blockIdx.y is the fold and its parameters, BN buffers, x, labels,
 // permutation and partial rows come from folds[blockIdx.y] (the pointer arguments are then unused).
 template <bool FOLD> struct FzFold {};
 template <> struct FzFold<true> { FoldCall fc; };
 
-template <int K1, int CC, int TT, int FF, bool BWD, bool FOLD = false>
+// STAGE (EEGNET_TRAIN_*): the first trainable module in network order.  The flat parameter buffer is in
+// network order, so the trainable set is the suffix [o_g2 | o_w2 | o_Wfc, nparam) of it, and the backward of
+// a trial stops as soon as the last sum of that suffix is complete:
+//     1 (aggregation)  ... dq -> dd2 -> dz2 for dg2 / db2 alone: no du, no dv / su sums, no dw1 correlation,
+//                      no ds', no dws product (and none of their registers: aWs, c1w, tapl)
+//     2 (block_2)      ... dW3, dq (registers) and dw2: no dd2, no dz2; dq is never stored
+//     3 (classifier)   the seed, dbfc, dWfc and the loss: no dz3, no LDS row reused
+// A cut instantiation writes only the partial-row columns of its suffix (FzCols unchanged: one workspace
+// serves every stage), and k_frozen_reduce reads only those.  What is computed is computed by the same
+// statements in the same order as in stage 0, so the suffix sums have the same bits.
+// Workgroup barriers of the backward, per stage (the forward's four are every stage's):
+//     q rows read: dr may land        stages 0-2   Qs is reused: every wave reads all q rows for dW3
+//     dr rows complete                stages 0-2   w3t_rows reads every wave's dr row
+//     dr rows read: dq may land       stages 0-1   stage 2 keeps dq in registers and leaves the dr rows alone
+//     ds' rows complete               stage 0      the dws product reads every ds' row
+//     x rows read (end of trial)      stage 0      the dws product is the last reader of Xs; in the cut
+//                                                  stages that is spatial_mfma, four barriers earlier
+//     next x stored (end of trial)    every stage  spatial_mfma of the next trial reads all x rows; it is
+//                                                  also what keeps Hs / Lg / Qs / D2s of this trial from the
+//                                                  next one's writers
+constexpr int FZ_ALL = 0, FZ_AGG = 1, FZ_B2 = 2, FZ_CLS = 3;
+template <int K1, int CC, int TT, int FF, bool BWD, bool FOLD = false, int STAGE = FZ_ALL>
 __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__ prm,
                                                 const float* __restrict__ bn, const float* __restrict__ x,
                                                 const float* __restrict__ dlog, const int64_t* __restrict__ lab,
@@ -152,9 +189,11 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
     // sums kept in registers across this workgroup's trials
     float aG3 = 0.f, aB3 = 0.f, aG2 = 0.f, aB2 = 0.f, aDV = 0.f, aSU = 0.f, aLoss = 0.f;
     float aFc[NCLS] = {0.f, 0.f, 0.f, 0.f}, aBfc[NCLS] = {0.f, 0.f, 0.f, 0.f};
-    floatx4 aWs[NCTM];
+    floatx4 aWs[STAGE == FZ_ALL ? NCTM : 1];            // (never touched by a cut stage)
+    if constexpr (STAGE == FZ_ALL) {
 #pragma unroll
-    for (int ct = 0; ct < NCTM; ++ct) aWs[ct] = (floatx4){0.f, 0.f, 0.f, 0.f};
+        for (int ct = 0; ct < NCTM; ++ct) aWs[ct] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    }
     const FzCols fc = fz_cols(g);
     float* const prow = BWD ? part + (size_t)blockIdx.x * fc.n : nullptr;
 
@@ -224,154 +263,177 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
 #pragma unroll
                 for (int n = 0; n < NCLS; ++n) aFc[n] = fmaf(gs[n], h, aFc[n]);
             }
-            float drv[MAXT1Q];
-            if (row_on) {
-                // dz3 = dh/8 m3/(1-p) ELU'(z3), dh = Wfc^T g; BN3 sums; dr = s3 dz3 (registers)
-                const float* wfc = prm + g.o_Wfc + o * T2;
+            if constexpr (STAGE < FZ_CLS) {
+                float drv[MAXT1Q];
+                if (row_on) {
+                    // dz3 = dh/8 m3/(1-p) ELU'(z3), dh = Wfc^T g; BN3 sums; dr = s3 dz3 (registers)
+                    const float* wfc = prm + g.o_Wfc + o * T2;
 #pragma unroll
-                for (int m = 0; m < MAXT1Q; ++m) {
-                    const int t = lane + 64 * m;
-                    float v = 0.f;
-                    if (t < 8 * T2) {
-                        float dh = 0.f;
+                    for (int m = 0; m < MAXT1Q; ++m) {
+                        const int t = lane + 64 * m;
+                        float v = 0.f;
+                        if (t < 8 * T2) {
+                            float dh = 0.f;
 #pragma unroll
-                        for (int n = 0; n < NCLS; ++n) dh = fmaf(wfc[n * NF + (t >> 3)], gs[n], dh);
-                        const float dz3 = 0.125f * dh * keep_mul(g, m3, key1, i3b + (unsigned)(t >> 3)) *
-                                          elu_d(fmaf(s3, r[m], b3));
-                        aG3 = fmaf(dz3, (r[m] - m3o) * i3, aG3);
-                        aB3 += dz3;
-                        v = s3 * dz3;
+                            for (int n = 0; n < NCLS; ++n) dh = fmaf(wfc[n * NF + (t >> 3)], gs[n], dh);
+                            const float dz3 = 0.125f * dh * keep_mul(g, m3, key1, i3b + (unsigned)(t >> 3)) *
+                                              elu_d(fmaf(s3, r[m], b3));
+                            aG3 = fmaf(dz3, (r[m] - m3o) * i3, aG3);
+                            aB3 += dz3;
+                            v = s3 * dz3;
+                        }
+                        drv[m] = v;
                     }
-                    drv[m] = v;
-                }
-                // dW3[o,i] += sum_t dr[o,t] q[i,t]
-                float cw[F2MAX];
+                    // dW3[o,i] += sum_t dr[o,t] q[i,t]
+                    float cw[F2MAX];
 #pragma unroll
-                for (int i = 0; i < F2MAX; ++i) cw[i] = 0.f;
+                    for (int i = 0; i < F2MAX; ++i) cw[i] = 0.f;
 #pragma unroll
-                for (int m = 0; m < MAXT1Q; ++m) {
-                    const int t = lane + 64 * m;
-                    if (t < 8 * T2) {
+                    for (int m = 0; m < MAXT1Q; ++m) {
+                        const int t = lane + 64 * m;
+                        if (t < 8 * T2) {
 #pragma unroll
-                        for (int i = 0; i < F2MAX; ++i)
-                            if (i < F2) cw[i] = fmaf(drv[m], Qs[i * RS2 + LP2 + t], cw[i]);
+                            for (int i = 0; i < F2MAX; ++i)
+                                if (i < F2) cw[i] = fmaf(drv[m], Qs[i * RS2 + LP2 + t], cw[i]);
+                        }
                     }
-                }
-                wave_reduce<F2MAX>(cw);                    // lane 16 r: sum[j + 4 r] in cw[j]
-                if (li == 0) {
-#pragma unroll
-                    for (int j = 0; j < F2MAX / 4; ++j) {
-                        const int i = j + (F2MAX / 4) * lk;
-                        if (i < F2) fz_add(prow + fc.W3 + o * F2 + i, cw[j], first);
-                    }
-                }
-            }
-            __syncthreads();                               // the q rows are read: dr may land on them
-            if (row_on) row_store(Qs + o * RS2 + LP2, T1, lane, drv);
-            __syncthreads();                               // dr rows complete
-            float dqv[MAXT1Q];
-            if (row_on) w3t_rows(prm + g.o_W3 + o, F2, T1, RS2, Qs + LP2, lane, dqv);
-            __syncthreads();                               // dr rows read: dq may land on them
-            if (row_on) {
-                row_store(Qs + o * RS2 + LP2, T1, lane, dqv);
-                // dw2[o,k] += sum_t dq[o,t] d2[o,t+k-7]
-                const float* dr = D2s + o * RS2 + 1;
-                float cw[K2];
-#pragma unroll
-                for (int k = 0; k < K2; ++k) cw[k] = 0.f;
-#pragma unroll
-                for (int m = 0; m < MAXT1Q; ++m) {
-                    const int t = lane + 64 * m;
-                    if (t < T1) {
-#pragma unroll
-                        for (int k = 0; k < K2; ++k) cw[k] = fmaf(dqv[m], dr[t + k], cw[k]);
-                    }
-                }
-                wave_reduce<K2>(cw);
-                if (li == 0) {
-#pragma unroll
-                    for (int j = 0; j < K2 / 4; ++j)
-                        fz_add(prow + fc.w2 + o * K2 + j + (K2 / 4) * lk, cw[j], first);
-                }
-                wave_lds_fence();
-                // dz2[4q + i] = dd2[q]/4 m2/(1-p) ELU'(z2[4q + i]); BN2 / BN1 sums; du = s2 dz2 over the v row
-                const float* qb = Qs + o * RS2 + (LP2 + 7);
-                float* vrow = Vs + o * RS + LP;
-                for (int q = lane; q < T1; q += 64) {
-                    float a = fir16_t(w.w2, qb, q);
-                    a *= 0.25f * keep_mul(g, m2, key0, i2b + (unsigned)q);
-                    const floatx4 v = lds_ld4(vrow + 4 * q);
-                    floatx4 du;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float dz2 = a * elu_d(fmaf(al, v[i], be));
-                        aG2 = fmaf(dz2, fmaf(ax, v[i], bx), aG2);
-                        aB2 += dz2;
-                        const float d = s2 * dz2;
-                        aDV = fmaf(d, v[i], aDV);
-                        aSU += d;
-                        du[i] = d;
-                    }
-                    lds_st4(vrow + 4 * q, du);
-                }
-                // (samples [4 T1, T) of the v row are never written: du is zero there, as it has to be)
-                wave_lds_fence();
-                // dw1 raw correlation: sum_t du[o,t] s[o,t+k-P], 32 lags at a time
-                const float* srow = Ss + o * RS;
-                constexpr int NWC = (G_::OFF + 32 + 6) / 4;
-#pragma unroll
-                for (int kc = 0; kc < K1; kc += 32) {
-                    float c1w[32];
-#pragma unroll
-                    for (int k = 0; k < 32; ++k) c1w[k] = 0.f;
-                    for (int q = lane; q < T1; q += 64) {
-                        float win[4 * NWC];
-                        lds_window<NWC>(srow + 4 * q + kc, win);
-                        const floatx4 du = lds_ld4(vrow + 4 * q);
-#pragma unroll
-                        for (int k = 0; k < 32; ++k)
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) c1w[k] = fmaf(du[i], win[G_::OFF + i + k], c1w[k]);
-                    }
-                    wave_reduce<32>(c1w);                  // lane 16 r: sum[j + 8 r] in c1w[j]
+                    wave_reduce<F2MAX>(cw);                    // lane 16 r: sum[j + 4 r] in cw[j]
                     if (li == 0) {
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) fz_add(prow + fc.w1 + o * K1 + kc + j + 8 * lk, c1w[j], first);
+                        for (int j = 0; j < F2MAX / 4; ++j) {
+                            const int i = j + (F2MAX / 4) * lk;
+                            if (i < F2) fz_add(prow + fc.W3 + o * F2 + i, cw[j], first);
+                        }
                     }
                 }
-                wave_lds_fence();
-                // ds' = FIR^T_w1(du) over the s row (its last reader was the correlation above)
-                temporal_row_t<K1>(Vs + o * RS, Ss + o * RS + LP, T, TQ, w.tap, tapl, lane);
-            }
-            __syncthreads();                               // ds' rows complete
-            // dws raw product sum_t ds'[o,t] x[c,t]: v_mfma_f32_16x16x4_f32, A = ds' tile (16 o x 4 t),
-            // B = x tile (4 t x 16 c), D[o = 4 (l >> 4) + r][c = 16 ct + (l & 15)]; wave w takes the
-            // 4-sample steps w, w + 16, ... and keeps its accumulators across the trials
-            for (int ks = wave; ks < TQ; ks += NWAVE) {
-                const int t = 4 * ks + lk;
-                const float av = li < F2 ? Ss[li * RS + LP + t] : 0.f;
+                __syncthreads();                               // the q rows are read: dr may land on them
+                if (row_on) row_store(Qs + o * RS2 + LP2, T1, lane, drv);
+                __syncthreads();                               // dr rows complete
+                float dqv[MAXT1Q];
+                if (row_on) w3t_rows(prm + g.o_W3 + o, F2, T1, RS2, Qs + LP2, lane, dqv);
+                if constexpr (STAGE < FZ_B2) __syncthreads();  // dr rows read: dq may land on them
+                if (row_on) {
+                    if constexpr (STAGE < FZ_B2) row_store(Qs + o * RS2 + LP2, T1, lane, dqv);
+                    // dw2[o,k] += sum_t dq[o,t] d2[o,t+k-7]
+                    const float* dr = D2s + o * RS2 + 1;
+                    float cw[K2];
 #pragma unroll
-                for (int ct = 0; ct < NCTM; ++ct) {
-                    if (ct < NCT) {
-                        const int c = 16 * ct + li;
-                        const float bv = c < C ? Xs[c * RS + LP + t] : 0.f;
-                        aWs[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, aWs[ct], 0, 0, 0);
+                    for (int k = 0; k < K2; ++k) cw[k] = 0.f;
+#pragma unroll
+                    for (int m = 0; m < MAXT1Q; ++m) {
+                        const int t = lane + 64 * m;
+                        if (t < T1) {
+#pragma unroll
+                            for (int k = 0; k < K2; ++k) cw[k] = fmaf(dqv[m], dr[t + k], cw[k]);
+                        }
+                    }
+                    wave_reduce<K2>(cw);
+                    if (li == 0) {
+#pragma unroll
+                        for (int j = 0; j < K2 / 4; ++j)
+                            fz_add(prow + fc.w2 + o * K2 + j + (K2 / 4) * lk, cw[j], first);
+                    }
+                    if constexpr (STAGE < FZ_B2) {
+                        wave_lds_fence();
+                        // dz2[4q + i] = dd2[q]/4 m2/(1-p) ELU'(z2[4q + i]); BN2 / BN1 sums; du = s2 dz2 over the v row
+                        const float* qb = Qs + o * RS2 + (LP2 + 7);
+                        float* vrow = Vs + o * RS + LP;
+                        for (int q = lane; q < T1; q += 64) {
+                            float a = fir16_t(w.w2, qb, q);
+                            a *= 0.25f * keep_mul(g, m2, key0, i2b + (unsigned)q);
+                            const floatx4 v = lds_ld4(vrow + 4 * q);
+                            floatx4 du;
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const float e = elu_d(fmaf(al, v[i], be));
+                                const float dz2 = a * e;
+                                aG2 = fmaf(dz2, fmaf(ax, v[i], bx), aG2);
+                                if constexpr (STAGE == FZ_ALL) aB2 += dz2;
+                                else aB2 = fz_b2_add<TT != 0>(aB2, a, e);
+                                if constexpr (STAGE == FZ_ALL) {
+                                    const float d = s2 * dz2;
+                                    aDV = fmaf(d, v[i], aDV);
+                                    aSU += d;
+                                    du[i] = d;
+                                }
+                            }
+                            if constexpr (STAGE == FZ_ALL) lds_st4(vrow + 4 * q, du);
+                        }
+                        if constexpr (STAGE == FZ_ALL) {
+                            // (samples [4 T1, T) of the v row are never written: du is zero there, as it has to be)
+                            wave_lds_fence();
+                            // dw1 raw correlation: sum_t du[o,t] s[o,t+k-P], 32 lags at a time
+                            const float* srow = Ss + o * RS;
+                            constexpr int NWC = (G_::OFF + 32 + 6) / 4;
+#pragma unroll
+                            for (int kc = 0; kc < K1; kc += 32) {
+                                float c1w[32];
+#pragma unroll
+                                for (int k = 0; k < 32; ++k) c1w[k] = 0.f;
+                                for (int q = lane; q < T1; q += 64) {
+                                    float win[4 * NWC];
+                                    lds_window<NWC>(srow + 4 * q + kc, win);
+                                    const floatx4 du = lds_ld4(vrow + 4 * q);
+#pragma unroll
+                                    for (int k = 0; k < 32; ++k)
+#pragma unroll
+                                        for (int i = 0; i < 4; ++i) c1w[k] = fmaf(du[i], win[G_::OFF + i + k], c1w[k]);
+                                }
+                                wave_reduce<32>(c1w);                  // lane 16 r: sum[j + 8 r] in c1w[j]
+                                if (li == 0) {
+#pragma unroll
+                                    for (int j = 0; j < 8; ++j)
+                                        fz_add(prow + fc.w1 + o * K1 + kc + j + 8 * lk, c1w[j], first);
+                                }
+                            }
+                            wave_lds_fence();
+                            // ds' = FIR^T_w1(du) over the s row (its last reader was the correlation above)
+                            temporal_row_t<K1>(Vs + o * RS, Ss + o * RS + LP, T, TQ, w.tap, tapl, lane);
+                        }
+                    }
+                }
+            }
+            if constexpr (STAGE == FZ_ALL) {
+                __syncthreads();                               // ds' rows complete
+                // dws raw product sum_t ds'[o,t] x[c,t]: v_mfma_f32_16x16x4_f32, A = ds' tile (16 o x 4 t),
+                // B = x tile (4 t x 16 c), D[o = 4 (l >> 4) + r][c = 16 ct + (l & 15)]; wave w takes the
+                // 4-sample steps w, w + 16, ... and keeps its accumulators across the trials
+                for (int ks = wave; ks < TQ; ks += NWAVE) {
+                    const int t = 4 * ks + lk;
+                    const float av = li < F2 ? Ss[li * RS + LP + t] : 0.f;
+#pragma unroll
+                    for (int ct = 0; ct < NCTM; ++ct) {
+                        if (ct < NCT) {
+                            const int c = 16 * ct + li;
+                            const float bv = c < C ? Xs[c * RS + LP + t] : 0.f;
+                            aWs[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, aWs[ct], 0, 0, 0);
+                        }
                     }
                 }
             }
         }
-        __syncthreads();                                   // x rows read: the next trial's x may land
+        // x rows read: the next trial's x may land (a cut stage's last reader of them is spatial_mfma)
+        if constexpr (!BWD || STAGE == FZ_ALL) __syncthreads();
         if (bnx < g.B) x_store<PF>(pf, C, T, RS, LP, Xs, tid);
         __syncthreads();
     }
 
     if constexpr (BWD) {
         // ---------------- publish this workgroup's partial row ----------------
-        aG3 = wave_sum(aG3); aB3 = wave_sum(aB3); aG2 = wave_sum(aG2); aB2 = wave_sum(aB2);
-        aDV = wave_sum(aDV); aSU = wave_sum(aSU);
-        if (row_on && lane == 0) {
-            prow[fc.g3 + o] = aG3; prow[fc.b3 + o] = aB3; prow[fc.g2 + o] = aG2; prow[fc.b2 + o] = aB2;
-            prow[fc.dv + o] = aDV; prow[fc.su + o] = aSU;
+        if constexpr (STAGE == FZ_ALL) {
+            aG3 = wave_sum(aG3); aB3 = wave_sum(aB3); aG2 = wave_sum(aG2); aB2 = wave_sum(aB2);
+            aDV = wave_sum(aDV); aSU = wave_sum(aSU);
+            if (row_on && lane == 0) {
+                prow[fc.g3 + o] = aG3; prow[fc.b3 + o] = aB3; prow[fc.g2 + o] = aG2; prow[fc.b2 + o] = aB2;
+                prow[fc.dv + o] = aDV; prow[fc.su + o] = aSU;
+            }
+        } else if constexpr (STAGE < FZ_CLS) {             // the columns of the trainable suffix alone
+            aG3 = wave_sum(aG3); aB3 = wave_sum(aB3);
+            if constexpr (STAGE == FZ_AGG) { aG2 = wave_sum(aG2); aB2 = wave_sum(aB2); }
+            if (row_on && lane == 0) {
+                prow[fc.g3 + o] = aG3; prow[fc.b3 + o] = aB3;
+                if constexpr (STAGE == FZ_AGG) { prow[fc.g2 + o] = aG2; prow[fc.b2 + o] = aB2; }
+            }
         }
         if (tid < NF) {
 #pragma unroll
@@ -383,6 +445,7 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
             prow[fc.loss] = aLoss;
         }
         // the waves' dws accumulators summed in wave order through the (free) x rows
+        if constexpr (STAGE == FZ_ALL) {
         for (int w = 0; w < NWAVE; ++w) {
             if (wave == w) {
 #pragma unroll
@@ -402,13 +465,17 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
             __syncthreads();
         }
         for (int i = tid; i < F2 * C; i += NTH) prow[fc.ws + i] = sm[i];
+        }   // STAGE == FZ_ALL
     }
 }
 
 // Sum of the partial rows over the workgroups, in workgroup order and fp64, turned into `grads` (flat
 // parameter layout) and `loss`.  One output element per lane; the four waves of a workgroup take a
 // quarter of the rows each and their sums are added in row order, so the result is a function of the
-// partial rows alone.
+// partial rows alone.  `off` is the first element of the trainable suffix (0: every parameter): the grid
+// covers [off, nparam] -- the suffix and the loss --, element e is computed as in the full launch whatever
+// `off`, and neither grads[0 : off) nor a partial-row column of a frozen parameter is touched (a cut
+// k_frozen leaves those columns unwritten).
 // FOLD: blockIdx.y is the fold, whose rows, parameters, BN buffers, `grads` and loss slot come from its record.
 constexpr int NTFR = 256, FR_OUT = 64;
 template <bool FOLD = false>
@@ -416,7 +483,7 @@ __global__ __launch_bounds__(NTFR) void k_frozen_reduce(Geo g, const float* __re
                                                         const float* __restrict__ bn,
                                                         const float* __restrict__ part, int nrows,
                                                         float* __restrict__ grads, float* __restrict__ loss,
-                                                        FzFold<FOLD> fold) {
+                                                        int off, FzFold<FOLD> fold) {
     if constexpr (FOLD) {
         const eegnet_fold f = fold_rec(fold.fc);
         prm = f.params; bn = f.bn_buffers; part = (const float*)f.ws; grads = f.grads;
@@ -425,7 +492,7 @@ __global__ __launch_bounds__(NTFR) void k_frozen_reduce(Geo g, const float* __re
     __shared__ double sh[NTFR / FR_OUT][FR_OUT];
     const FzCols fc = fz_cols(g);
     const int tid = threadIdx.x, le = tid & (FR_OUT - 1), qd = tid / FR_OUT;
-    const int e = blockIdx.x * FR_OUT + le;
+    const int e = off + blockIdx.x * FR_OUT + le;
     const int w0 = (int)((long long)qd * nrows / (NTFR / FR_OUT)), w1 = (int)((long long)(qd + 1) * nrows / (NTFR / FR_OUT));
     auto col = [&](int c) {
         double s = 0.0;
@@ -496,12 +563,13 @@ __global__ __launch_bounds__(NTFR) void k_frozen_reduce(Geo g, const float* __re
 // k_adam for every fold of a fold-indexed frozen step (blockIdx.y the fold): the same element update with
 // the same scalars, so a fold's parameters and Adam state come out as eegnet_adam_step leaves them.  A
 // fold without Adam state keeps its parameters.  The step counters are advanced by k_step_inc_folds, a
-// launch of its own behind this one: every workgroup here reads its fold's counter.
-__global__ __launch_bounds__(256) void k_adam_folds(int64_t n, FoldCall fc) {
+// launch of its own behind this one: every workgroup here reads its fold's counter.  Elements [off, n) are
+// updated (off: the first trainable element); parameters and both moments below `off` are not touched.
+__global__ __launch_bounds__(256) void k_adam_folds(int64_t n, int64_t off, FoldCall fc) {
     const eegnet_fold f = fold_rec(fc);
     if (!f.adam_state) return;
     const int s = *f.step + 1;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = off + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
         const float step_size = (float)((double)fc.lr / (1.0 - pow((double)fc.b1, (double)s)));
         const float bc2s = (float)sqrt(1.0 - pow((double)fc.b2, (double)s));

@@ -325,6 +325,14 @@ static void set_attrs_shape() {
     hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_frozen<K1, CC, TT, FF, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    // the cut backward stages (eegnet_frozen_step_from / _folds_from), single model and fold-indexed
+    for (const void* f : {(const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_AGG>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_B2>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_CLS>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_AGG>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_B2>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_CLS>})
+        hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_eval_folds<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
@@ -919,17 +927,45 @@ static int frozen_geo(const eegnet_dims* dims, Geo* g) {
 
 static size_t frozen_ws_bytes(const Geo& g) { return rupz((size_t)g.grid * fz_cols(g).n * 4, 256); }
 
-static int frozen_launch(const char* name, const Geo& g, bool bwd, const float* params, const float* bn,
-                         const float* x, const float* dlogits, const int64_t* labels, const uint8_t* m2,
-                         const uint8_t* m3, float* logits, float* part, hipStream_t s) {
+// the backward instantiation of a shape for train_from (EEGNET_TRAIN_*, validated by frozen_offset)
+template <int K1, int CC, int TT, int FF, bool FOLD>
+static auto frozen_bwd_kernel(int train_from) {
+    switch (train_from) {
+        case EEGNET_TRAIN_FROM_AGGREGATION: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_AGG>;
+        case EEGNET_TRAIN_FROM_BLOCK2: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_B2>;
+        case EEGNET_TRAIN_FROM_CLASSIFIER: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_CLS>;
+        default: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_ALL>;
+    }
+}
+
+static int frozen_launch(const char* name, const Geo& g, bool bwd, int train_from, const float* params,
+                         const float* bn, const float* x, const float* dlogits, const int64_t* labels,
+                         const uint8_t* m2, const uint8_t* m3, float* logits, float* part, hipStream_t s) {
     return dispatch_shape(g, [&](auto sh) {
-        return launch(KID_NONE, name, bwd ? k_frozen<SHAPE_OF(sh), true> : k_frozen<SHAPE_OF(sh), false>, dim3(g.grid),
-                      dim3(NTH), g.ldsX * 4, s, g, params, bn, x, dlogits, labels, m2, m3, logits, part, FzFold<false>{});
+        return launch(KID_NONE, name,
+                      bwd ? frozen_bwd_kernel<SHAPE_OF(sh), false>(train_from) : k_frozen<SHAPE_OF(sh), false>,
+                      dim3(g.grid), dim3(NTH), g.ldsX * 4, s, g, params, bn, x, dlogits, labels, m2, m3, logits, part,
+                      FzFold<false>{});
     });
 }
 
-// workgroups of k_frozen_reduce: FR_OUT outputs each over the gradients and the loss
-static unsigned frozen_reduce_grid(const Geo& g) { return (unsigned)((g.nparam + 1 + FR_OUT - 1) / FR_OUT); }
+// first element of the trainable suffix of the flat parameters for train_from: the flat buffer is in
+// network order, so freezing every module before one freezes a prefix of it
+static int frozen_offset(const Geo& g, int train_from, int* off) {
+    switch (train_from) {
+        case EEGNET_TRAIN_ALL: *off = 0; return 0;
+        case EEGNET_TRAIN_FROM_AGGREGATION: *off = g.o_g2; return 0;
+        case EEGNET_TRAIN_FROM_BLOCK2: *off = g.o_w2; return 0;
+        case EEGNET_TRAIN_FROM_CLASSIFIER: *off = g.o_Wfc; return 0;
+    }
+    return fail(EEGNET_EINVAL, "train_from must be EEGNET_TRAIN_ALL (0), EEGNET_TRAIN_FROM_AGGREGATION (1), "
+                "EEGNET_TRAIN_FROM_BLOCK2 (2) or EEGNET_TRAIN_FROM_CLASSIFIER (3) (got %d)", train_from);
+}
+
+// workgroups of k_frozen_reduce: FR_OUT outputs each over the gradients from `off` on and the loss
+static unsigned frozen_reduce_grid(const Geo& g, int off = 0) {
+    return (unsigned)((g.nparam - off + 1 + FR_OUT - 1) / FR_OUT);
+}
 
 extern "C" {
 
@@ -951,17 +987,19 @@ int eegnet_forward_frozen(const eegnet_dims* dims, const float* params, const fl
     if ((g.T & 3) == 0 && ((uintptr_t)x & 15)) return fail(EEGNET_EINVAL, "frozen BatchNorm: x must be 16-byte aligned");
     set_key(&g, seed, offset);
     ensure_attrs();
-    return frozen_launch("k_frozen(fwd)", g, false, params, bn_buffers, x, nullptr, nullptr, mask2, mask3, logits,
-                         nullptr, (hipStream_t)stream);
+    return frozen_launch("k_frozen(fwd)", g, false, EEGNET_TRAIN_ALL, params, bn_buffers, x, nullptr, nullptr, mask2,
+                         mask3, logits, nullptr, (hipStream_t)stream);
 }
 
-int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,
-                       const float* dlogits, const int64_t* labels, const uint8_t* mask2,
-                       const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads,
-                       float* adam_state, int32_t* step, float lr, float beta1, float beta2, float eps,
-                       float* loss, float* logits, void* ws, void* stream, int flags) {
+int eegnet_frozen_step_from(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,
+                            const float* dlogits, const int64_t* labels, const uint8_t* mask2,
+                            const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads,
+                            float* adam_state, int32_t* step, float lr, float beta1, float beta2, float eps,
+                            float* loss, float* logits, void* ws, void* stream, int flags, int train_from) {
     Geo g;
     if (int r = frozen_geo(dims, &g)) return r;
+    int off;
+    if (int r = frozen_offset(g, train_from, &off)) return r;
     if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
     if (int r = check_ptrs(x, "x", grads, "grads")) return r;
     if (int r = check_ptrs(ws, "ws")) return r;
@@ -975,26 +1013,49 @@ int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_b
     ensure_attrs();
     hipStream_t s = (hipStream_t)stream;
     float* part = (float*)ws;
-    if (int r = frozen_launch("k_frozen", g, true, params, bn_buffers, x, dlogits, labels, mask2, mask3, logits, part, s))
+    if (int r = frozen_launch("k_frozen", g, true, train_from, params, bn_buffers, x, dlogits, labels, mask2, mask3,
+                              logits, part, s))
         return r;
-    if (int r = launch(KID_NONE, "k_frozen_reduce", k_frozen_reduce<false>, dim3(frozen_reduce_grid(g)),
-                       dim3(NTFR), 0, s, g, params, bn_buffers, part, g.grid, grads, loss, FzFold<false>{})) return r;
+    if (int r = launch(KID_NONE, "k_frozen_reduce", k_frozen_reduce<false>, dim3(frozen_reduce_grid(g, off)),
+                       dim3(NTFR), 0, s, g, params, bn_buffers, part, g.grid, grads, loss, off, FzFold<false>{})) return r;
     if (!adam_state) return 0;
-    // the Adam kernel of eegnet_adam_step behind the reduction; it advances the step counter last, after
-    // k_frozen has read it for the dropout key (EEGNET_KEY_FROM_STEP)
-    return eegnet_adam_step(g.nparam, params, grads, adam_state, adam_state + g.nparam, step, lr, beta1, beta2,
-                            eps, stream);
+    // the Adam kernel of eegnet_adam_step behind the reduction, over the trainable suffix; it advances the
+    // step counter last, after k_frozen has read it for the dropout key (EEGNET_KEY_FROM_STEP)
+    return eegnet_adam_step(g.nparam - off, params + off, grads + off, adam_state + off, adam_state + g.nparam + off,
+                            step, lr, beta1, beta2, eps, stream);
+}
+
+int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,
+                       const float* dlogits, const int64_t* labels, const uint8_t* mask2,
+                       const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads,
+                       float* adam_state, int32_t* step, float lr, float beta1, float beta2, float eps,
+                       float* loss, float* logits, void* ws, void* stream, int flags) {
+    return eegnet_frozen_step_from(dims, params, bn_buffers, x, dlogits, labels, mask2, mask3, seed, offset, grads,
+                                   adam_state, step, lr, beta1, beta2, eps, loss, logits, ws, stream, flags,
+                                   EEGNET_TRAIN_ALL);
+}
+
+int eegnet_trainable_offset(const eegnet_dims* dims, int train_from, int64_t* out) {
+    Geo g;
+    if (int r = frozen_geo(dims, &g)) return r;
+    int off;
+    if (int r = frozen_offset(g, train_from, &off)) return r;
+    if (!out) return fail(EEGNET_EINVAL, "out is NULL");
+    *out = off;
+    return 0;
 }
 
 // One frozen-BatchNorm iteration of nfolds models in four launches, whatever nfolds: k_frozen and
 // k_frozen_reduce with the fold in the grid's y, then Adam and the step counters.  The per-fold grid is
 // eegnet_frozen_step's for the same dims (g.grid, a function of B alone), so a fold's partial rows -- and
 // with them every bit of its result -- are those of that call on the fold alone.
-int eegnet_frozen_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
-                             int64_t slot, uint64_t offset, float lr, float beta1, float beta2, float eps,
-                             int flags, void* stream) {
+int eegnet_frozen_step_folds_from(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
+                                  int64_t slot, uint64_t offset, float lr, float beta1, float beta2, float eps,
+                                  int flags, void* stream, int train_from) {
     Geo g;
     if (int r = frozen_geo(dims, &g)) return r;
+    int off;
+    if (int r = frozen_offset(g, train_from, &off)) return r;
     if (nfolds < 1 || nfolds > 65535) return fail(EEGNET_EINVAL, "nfolds must be in [1, 65535] (got %d)", nfolds);
     if (!folds) return fail(EEGNET_EINVAL, "folds is NULL");
     if (row0 < 0 || slot < 0) return fail(EEGNET_EINVAL, "row0 / slot must be >= 0");
@@ -1013,17 +1074,24 @@ int eegnet_frozen_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_f
     const unsigned nf = (unsigned)nfolds;
     const FzFold<true> fold{fc};
     if (int r = dispatch_shape(g, [&](auto sh) {
-            return launch(KID_NONE, "k_frozen(folds)", k_frozen<SHAPE_OF(sh), true, true>, dim3(g.grid, nf), dim3(NTH),
-                          g.ldsX * 4, s, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+            return launch(KID_NONE, "k_frozen(folds)", frozen_bwd_kernel<SHAPE_OF(sh), true>(train_from), dim3(g.grid, nf),
+                          dim3(NTH), g.ldsX * 4, s, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                           nullptr, fold);
         })) return r;
-    if (int r = launch(KID_NONE, "k_frozen_reduce(folds)", k_frozen_reduce<true>, dim3(frozen_reduce_grid(g), nf),
-                       dim3(NTFR), 0, s, g, nullptr, nullptr, nullptr, g.grid, nullptr, nullptr, fold)) return r;
+    if (int r = launch(KID_NONE, "k_frozen_reduce(folds)", k_frozen_reduce<true>, dim3(frozen_reduce_grid(g, off), nf),
+                       dim3(NTFR), 0, s, g, nullptr, nullptr, nullptr, g.grid, nullptr, nullptr, off, fold)) return r;
     // every reader of the step counters -- the dropout keys above, Adam's bias correction -- is in an
     // earlier launch than their increment
-    if (int r = launch(KID_NONE, "k_adam_folds", k_adam_folds, dim3((unsigned)((g.nparam + 255) / 256), nf), dim3(256),
-                       0, s, (int64_t)g.nparam, fc)) return r;
+    if (int r = launch(KID_NONE, "k_adam_folds", k_adam_folds, dim3((unsigned)((g.nparam - off + 255) / 256), nf),
+                       dim3(256), 0, s, (int64_t)g.nparam, (int64_t)off, fc)) return r;
     return launch(KID_NONE, "k_step_inc_folds", k_step_inc_folds, dim3((nf + 255) / 256), dim3(256), 0, s, fc, nfolds);
+}
+
+int eegnet_frozen_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
+                             int64_t slot, uint64_t offset, float lr, float beta1, float beta2, float eps,
+                             int flags, void* stream) {
+    return eegnet_frozen_step_folds_from(dims, nfolds, folds, row0, slot, offset, lr, beta1, beta2, eps, flags, stream,
+                                         EEGNET_TRAIN_ALL);
 }
 
 }  // extern "C"

@@ -450,7 +450,12 @@ class FrozenFoldBatch(_FoldStreams):
     fold index in the grid, the epoch's shuffle read through per-fold permutations, x in place); the
     per-fold path runs ``ops.frozen_step`` on the epoch's gathered rows, one HIP stream per fold.  Both
     key the dropout masks by (fold seed, device Adam step) and split a fold's batch over workgroups by
-    the batch size alone, so they agree bit for bit, with and without ``graphs``."""
+    the batch size alone, so they agree bit for bit, with and without ``graphs``.
+
+    Partial fine-tuning (``EEGNet.train_from``): every epoch derives each model's stage from its
+    ``requires_grad`` flags; a fold's backward stops at its frozen prefix, whose parameters and Adam
+    state are never written.  The fused launches take one stage for all folds: with mixed stages
+    ``fused=True`` is a ValueError and ``fused=None`` runs the per-fold path, each fold at its own stage."""
 
     def __init__(self, models: list[EEGNet], seeds: list[int], lr=1e-3, betas=(0.9, 0.999),
                  eps=1e-7, graphs=False, fused=None):
@@ -475,8 +480,26 @@ class FrozenFoldBatch(_FoldStreams):
         same = all(m.shape == models[0].shape for m in models) and models[0].shape.F2 <= 16
         if fused and not same:
             raise ValueError("fused fold launches need the same EEGNet shape (F1*D <= 16) for every fold")
+        self._auto = fused is None
         self.fused = (same and len(models) >= self.FUSED_MIN_FOLDS) if fused is None else bool(fused)
         self._fz = None                     # fused-launch state: buffers, fold tables, graph
+        self._stages = None
+        self._derive_stages()
+
+    def _derive_stages(self):
+        """Each model's stage from its ``requires_grad`` flags (NotImplementedError for a pattern that is
+        no frozen prefix).  A change drops what was captured with the old stages; returns whether the
+        fused launches apply (one stage for every fold)."""
+        stages = tuple(m.trainable_stage() for m in self.models)
+        if stages != self._stages:
+            self._stages = stages
+            self._fz = None
+            self._graph = [None] * len(self.models)
+        uniform = len(set(stages)) == 1
+        if self.fused and not uniform and not self._auto:
+            raise ValueError(f"fused fold launches need the same trainable stage for every fold (got "
+                             f"{[ops.STAGES[s] for s in stages]}): pass fused=None or fused=False")
+        return self.fused and uniform
 
     # fused=None takes the fused launches from this many folds on: profiles/frozen_folds_bench.json has
     # them no slower than the per-fold path at every K measured (12, 36, 90), and nothing below 12
@@ -500,7 +523,8 @@ class FrozenFoldBatch(_FoldStreams):
             xb, yb = Xp[i:i + batch_size], yp[i:i + batch_size]
             ops.frozen_step(m.shape, flat, bn, xb, self.seeds[k], 0, a.grads, self._workspace(k, xb.shape[0]),
                             labels=yb, adam_state=a.state, step_i32=a.step, loss=losses[j:j + 1],
-                            lr=self.lr, betas=self.betas, eps=self.eps, key_from_step=True)
+                            lr=self.lr, betas=self.betas, eps=self.eps, key_from_step=True,
+                            train_from=self._stages[k])
 
     def _fused_state(self, data, batch_size):
         X0, _ = data[0]
@@ -546,7 +570,7 @@ class FrozenFoldBatch(_FoldStreams):
         K = len(self.models)
         for i, j, B in st["steps"]:
             ops.frozen_step_folds(shape, B, st["tables"][B], K, row0=i, slot=j, offset=0, lr=self.lr,
-                                  betas=self.betas, eps=self.eps)
+                                  betas=self.betas, eps=self.eps, train_from=self._stages[0])
 
     def epoch(self, data: list[tuple[torch.Tensor, torch.Tensor]], batch_size: int = 64,
               generators: list[torch.Generator] | None = None) -> list[torch.Tensor]:
@@ -558,7 +582,7 @@ class FrozenFoldBatch(_FoldStreams):
         _require_frozen(self.models)
         if len(data) != len(self.models):
             raise ValueError("one (X, y) per fold")
-        if self.fused and all(X.shape[0] == data[0][0].shape[0] for X, _ in data):
+        if self._derive_stages() and all(X.shape[0] == data[0][0].shape[0] for X, _ in data):
             st = self._fused_state(data, batch_size)
             _stage_permutations(st, data[0][0].shape[0], generators)
             return _run_epoch(st, lambda: self._fused_steps(st), self.graphs)

@@ -203,6 +203,62 @@ class EEGNet(nn.Module):
         self.bn_frozen = bool(mode)
         return self
 
+    # -- partial fine-tuning: a frozen prefix of the layers ----------------------------------------
+    # the first parameter (named_parameters() order) of each stage of ops.STAGES
+    _STAGE_FIRST = {"temporal": "temporal.0.weight", "aggregation": "aggregation.0.weight",
+                    "block_2": "block_2.0.weight", "classifier": "classifier.weight"}
+
+    def train_from(self, stage):
+        """Train the modules from ``stage`` on and freeze every module before it: ``"temporal"``
+        (everything trains), ``"aggregation"`` (the temporal block and the spatial filters are kept),
+        ``"block_2"`` (and the second BatchNorm's affine pair) or ``"classifier"`` (the classifier
+        alone).  Sets ``requires_grad`` False on the prefix and True on the suffix, as a caller would on
+        a stock module.  With ``freeze_bn()`` set, the train-mode backward, ``FusedTrainer`` / ``train()``
+        and ``FrozenFoldBatch`` then run a backward that stops where the trainable layers stop, leave
+        ``grad`` of the frozen parameters ``None`` and never write them or their Adam state.  Without
+        ``freeze_bn()`` nothing changes: the five-pass train step ignores ``requires_grad`` (it computes
+        and, fused, applies all 12 gradients), as it always has.  Returns self."""
+        s = ops.stage_index(stage)
+        if not 0 <= s < len(ops.STAGES):
+            raise ValueError(f"stage must be one of {list(ops.STAGES)} (got {stage!r})")
+        first = self._STAGE_FIRST[ops.STAGES[s]]
+        on = False
+        for name, p in self.named_parameters():
+            on = on or name == first
+            p.requires_grad_(on)
+        return self
+
+    def trainable_stage(self) -> int:
+        """The stage (index into ``ops.STAGES``) the parameters' ``requires_grad`` flags spell: 0 when
+        every parameter trains, else the first trainable module of a frozen-prefix pattern as
+        ``train_from`` sets it.  Any other pattern raises NotImplementedError."""
+        named = list(self.named_parameters())
+        flags = [p.requires_grad for _, p in named]
+        if all(flags):
+            return 0
+        starts = {name: i for i, name in enumerate(self._STAGE_FIRST.values())}
+        first = flags.index(True) if any(flags) else None
+        if first is None:
+            bad, why = named[-1][0], "no parameter is trainable"
+        elif named[first][0] not in starts:
+            bad, why = named[first][0], "it is trainable while the parameters before it are frozen, and no stage begins there"
+        elif not all(flags[first:]):
+            bad = named[first + flags[first:].index(False)][0]
+            why = f"it is frozen behind the trainable {named[first][0]}"
+        else:
+            return starts[named[first][0]]
+        raise NotImplementedError(
+            f"partial fine-tuning trains a suffix of the layers: {bad} does not fit ({why}); the supported "
+            f"stages are {', '.join(ops.STAGES)} (EEGNet.train_from)")
+
+    def _stage_checked(self) -> int:
+        """``trainable_stage()`` for a caller that has just made the layout check (``flat_views``): the
+        usual case, every parameter trainable, without walking the module tree."""
+        for p in self._plist:
+            if not p.requires_grad:
+                return self.trainable_stage()
+        return 0
+
     # -- dropout control (test hook) ------------------------------------------------------------
     def set_dropout_masks(self, m2, m3):
         """Inject keep-masks ([B,F2,T//4], [B,F2,T//128] uint8, 1 = keep) for the train-mode
@@ -253,7 +309,11 @@ class EEGNet(nn.Module):
             if masks is not None and masks[0].shape[0] != x.shape[0]:
                 raise RuntimeError("injected dropout masks do not match the batch size")
             if getattr(self, "bn_frozen", False):
-                return _FrozenTrainFn.apply(x, self, shape, seed, offset, masks, *params)
+                # the stage the backward will run at (an unsupported pattern raises here: nothing ran); 0
+                # when nothing will be differentiated
+                diff = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+                stage = self._stage_checked() if diff else 0
+                return _FrozenTrainFn.apply(x, self, shape, seed, offset, masks, stage, *params)
             return _TrainFn.apply(x, self, shape, seed, offset, masks, *params)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             return _EvalFn.apply(x, self, shape, *params)
@@ -304,7 +364,7 @@ class _FrozenTrainFn(torch.autograd.Function):
     forward that ran: parameters, running statistics, masks and dropout key are those of forward time."""
 
     @staticmethod
-    def forward(ctx, x, mod, shape, seed, offset, masks, *params):
+    def forward(ctx, x, mod, shape, seed, offset, masks, stage, *params):
         flat = mod.flat_parameters().clone()
         bn_flat = mod.flat_bn_buffers().clone()
         try:
@@ -313,6 +373,7 @@ class _FrozenTrainFn(torch.autograd.Function):
             _not_supported(e)
         ctx.shape, ctx.seed, ctx.offset, ctx.masks = shape, seed, offset, masks
         ctx.param_shapes = [p.shape for p in params]
+        ctx.stage = stage
         ctx.save_for_backward(x, flat, bn_flat)
         return logits
 
@@ -321,15 +382,17 @@ class _FrozenTrainFn(torch.autograd.Function):
         x, flat, bn_flat = ctx.saved_tensors
         ws = ops.new_frozen_workspace(ctx.shape, x.shape[0], x.device)
         g = ops.frozen_step(ctx.shape, flat, bn_flat, x, ctx.seed, ctx.offset, torch.empty_like(flat), ws,
-                            dlogits=dlogits.contiguous().float(), masks=ctx.masks)
+                            dlogits=dlogits.contiguous().float(), masks=ctx.masks, train_from=ctx.stage)
+        # the cut step leaves g below the trainable suffix unwritten: None for the frozen parameters
+        off = ops.trainable_offset(ctx.shape, ctx.stage) if ctx.stage else 0
         out, o = [], 0
         for s in ctx.param_shapes:
             k = 1
             for d in s:
                 k *= d
-            out.append(g[o:o + k].view(s))
+            out.append(g[o:o + k].view(s) if o >= off else None)
             o += k
-        return (None, None, None, None, None, None, *out)
+        return (None, None, None, None, None, None, None, *out)
 
 
 class _EvalFn(torch.autograd.Function):
@@ -435,8 +498,18 @@ def _fusable(model, optimizer, loss_fn) -> bool:
     if len(optimizer.param_groups) != 1:
         return False
     grp = optimizer.param_groups[0]
-    if [id(p) for p in grp["params"]] != [id(p) for p in model.parameters()]:
-        return False
+    ids, want = [id(p) for p in grp["params"]], [id(p) for p in model.parameters()]
+    if ids != want:
+        # partial fine-tuning with frozen BatchNorm: an optimizer over exactly the trainable suffix
+        # (Adam(filter(lambda p: p.requires_grad, model.parameters())) after EEGNet.train_from)
+        if not getattr(model, "bn_frozen", False):
+            return False
+        try:
+            stage = model.trainable_stage()
+        except NotImplementedError:
+            return False                    # (the autograd path raises it at the first forward)
+        if stage == 0 or ids != [id(p) for p in model.parameters() if p.requires_grad]:
+            return False
     if grp["weight_decay"] != 0 or grp["amsgrad"] or grp.get("maximize", False):
         return False
     if isinstance(grp["lr"], torch.Tensor) or grp.get("differentiable", False):
@@ -456,12 +529,18 @@ class FusedAdamState:
         if optimizer is not None:
             self.load_from(model, optimizer)
 
+    @staticmethod
+    def _skips(model, p) -> bool:
+        """A parameter the fused frozen-BatchNorm step never touches (EEGNet.train_from): stock Adam
+        keeps no state for a parameter whose grad stays None, and neither does the synchronisation."""
+        return getattr(model, "bn_frozen", False) and not p.requires_grad
+
     def load_from(self, model, optimizer):
         n = model.flat_parameters().numel()
         o = 0
         steps = set()
         for p in model.parameters():
-            st = optimizer.state.get(p, {})
+            st = {} if self._skips(model, p) else optimizer.state.get(p, {})
             k = p.numel()
             if "exp_avg" in st:
                 self.state[o:o + k].copy_(st["exp_avg"].reshape(-1))
@@ -478,6 +557,9 @@ class FusedAdamState:
         o = 0
         for p in model.parameters():
             k = p.numel()
+            if self._skips(model, p):
+                o += k
+                continue
             st = optimizer.state[p]
             st["step"] = torch.tensor(float(step))
             st["exp_avg"] = self.state[o:o + k].view(p.shape).clone()
@@ -522,11 +604,12 @@ class FusedTrainer:
             masks = m._masks
             if masks is not None and masks[0].shape[0] != x.shape[0]:
                 raise RuntimeError("injected dropout masks do not match the batch size")
+            stage = m._stage_checked()      # EEGNet.train_from: the backward and Adam stop at the frozen prefix
             try:
                 ops.frozen_step(m.shape, flat, bn_flat, x.contiguous(), seed, offset, self.adam.grads,
                                 self.frozen_workspace(x.shape[0]), labels=y, masks=masks,
                                 adam_state=self.adam.state, step_i32=self.adam.step, loss=self.loss,
-                                logits=logits, lr=self.lr, betas=self.betas, eps=self.eps)
+                                logits=logits, lr=self.lr, betas=self.betas, eps=self.eps, train_from=stage)
             except RuntimeError as e:
                 _not_supported(e)
             return self.loss

@@ -229,23 +229,53 @@ def forward_frozen(shape: Shape, flat_params, bn_flat, x, seed: int, offset: int
     return logits
 
 
+# include/eegnet_abi.h EEGNET_TRAIN_*: the first trainable module of a partial fine-tuning step, by name
+STAGES = ("temporal", "aggregation", "block_2", "classifier")
+
+
+def stage_index(stage) -> int:
+    """0..3 for a stage given as its index or its name in ``STAGES``."""
+    if isinstance(stage, str):
+        if stage not in STAGES:
+            raise ValueError(f"stage must be one of {list(STAGES)} (got {stage!r})")
+        return STAGES.index(stage)
+    return int(stage)
+
+
+def trainable_offset(shape: Shape, stage) -> int:
+    """eegnet_trainable_offset: the first element of the flat parameters that a frozen-BatchNorm step
+    with ``train_from=stage`` trains (everything from that module on; 0 for "temporal").  Host-side
+    geometry only."""
+    out = ctypes.c_int64(0)
+    _lib.check(_lib.load().eegnet_trainable_offset(ctypes.byref(shape.dims(1)), ctypes.c_int(stage_index(stage)),
+                                                   ctypes.byref(out)), "eegnet_trainable_offset")
+    return int(out.value)
+
+
 def frozen_step(shape: Shape, flat_params, bn_flat, x, seed: int, offset: int, grads, ws, *, dlogits=None,
                 labels=None, masks=None, adam_state=None, step_i32=None, loss=None, logits=None, lr=1e-3,
-                betas=(0.9, 0.999), eps=1e-7, p: float | None = None, clamp=True, key_from_step=False):
+                betas=(0.9, 0.999), eps=1e-7, p: float | None = None, clamp=True, key_from_step=False,
+                train_from=0):
     """One frozen-BatchNorm iteration (eegnet_frozen_step) on the device, no host sync: forward, the
     seed (``dlogits`` [B, 4], or mean cross-entropy against ``labels`` with the loss written to
     ``loss``), backward and all 12 parameter gradients into ``grads``; with ``adam_state`` the Adam
     update follows on the same stream.  ``x`` must be contiguous [B, C, T]; ``ws`` from
-    ``new_frozen_workspace``."""
+    ``new_frozen_workspace``.  ``train_from`` (a stage of ``STAGES``, by index or name) other than 0
+    trains the modules from that one on (eegnet_frozen_step_from): the backward stops there, and
+    ``grads``, the parameters and the Adam moments below ``trainable_offset`` are not written."""
     if not x.is_contiguous():
         raise ValueError("frozen_step takes a contiguous [B, C, T] x")
     m2, m3 = masks if masks is not None else (None, None)
-    _lib.check(_lib.load().eegnet_frozen_step(
-        ctypes.byref(shape.dims(x.shape[0], p)), _ptr(flat_params), _ptr(bn_flat), _ptr(x), _ptr(dlogits),
-        _ptr(labels), _ptr(m2), _ptr(m3), ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(grads),
-        _ptr(adam_state), _ptr(step_i32), ctypes.c_float(lr), ctypes.c_float(betas[0]),
-        ctypes.c_float(betas[1]), ctypes.c_float(eps), _ptr(loss), _ptr(logits), _ptr(ws), _stream(),
-        (0 if clamp else NO_CLAMP) | (KEY_FROM_STEP if key_from_step else 0)), "eegnet_frozen_step")
+    stage = stage_index(train_from)
+    args = (ctypes.byref(shape.dims(x.shape[0], p)), _ptr(flat_params), _ptr(bn_flat), _ptr(x), _ptr(dlogits),
+            _ptr(labels), _ptr(m2), _ptr(m3), ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(grads),
+            _ptr(adam_state), _ptr(step_i32), ctypes.c_float(lr), ctypes.c_float(betas[0]),
+            ctypes.c_float(betas[1]), ctypes.c_float(eps), _ptr(loss), _ptr(logits), _ptr(ws), _stream(),
+            (0 if clamp else NO_CLAMP) | (KEY_FROM_STEP if key_from_step else 0))
+    if stage == 0:
+        _lib.check(_lib.load().eegnet_frozen_step(*args), "eegnet_frozen_step")
+    else:
+        _lib.check(_lib.load().eegnet_frozen_step_from(*args, ctypes.c_int(stage)), "eegnet_frozen_step_from")
     return grads
 
 
@@ -393,18 +423,23 @@ def train_step_folds(shape: Shape, B: int, table: torch.Tensor, nfolds: int, row
 
 def frozen_step_folds(shape: Shape, B: int, table: torch.Tensor, nfolds: int, row0: int, slot: int,
                       offset: int = 0, lr=1e-3, betas=(0.9, 0.999), eps=1e-7, p: float | None = None,
-                      clamp=True):
+                      clamp=True, train_from=0):
     """eegnet_frozen_step_folds: one frozen-BatchNorm iteration (``frozen_step`` with labels and
     ``key_from_step``) of ``nfolds`` independent models in four launches, the fold index in the grid's
     y.  ``table`` from fold_table(); every fold trains on rows perm[row0 : row0 + B] (rows
     [row0, row0 + B) without a perm) of its own contiguous x / labels, writes its loss to
     losses[slot] and keeps its partial rows in its own ``ws`` (``new_frozen_workspace``); a fold
-    without ``adam_state`` stops after its gradients.  BN buffers are read only."""
-    _lib.check(_lib.load().eegnet_frozen_step_folds(
-        ctypes.byref(shape.dims(B, p)), ctypes.c_int(nfolds), _ptr(table), ctypes.c_int64(row0),
-        ctypes.c_int64(slot), ctypes.c_uint64(offset), ctypes.c_float(lr), ctypes.c_float(betas[0]),
-        ctypes.c_float(betas[1]), ctypes.c_float(eps), ctypes.c_int(0 if clamp else NO_CLAMP), _stream()),
-        "eegnet_frozen_step_folds")
+    without ``adam_state`` stops after its gradients.  BN buffers are read only.  ``train_from`` other
+    than 0: every fold trains the modules from that stage on (eegnet_frozen_step_folds_from)."""
+    stage = stage_index(train_from)
+    args = (ctypes.byref(shape.dims(B, p)), ctypes.c_int(nfolds), _ptr(table), ctypes.c_int64(row0),
+            ctypes.c_int64(slot), ctypes.c_uint64(offset), ctypes.c_float(lr), ctypes.c_float(betas[0]),
+            ctypes.c_float(betas[1]), ctypes.c_float(eps), ctypes.c_int(0 if clamp else NO_CLAMP), _stream())
+    if stage == 0:
+        _lib.check(_lib.load().eegnet_frozen_step_folds(*args), "eegnet_frozen_step_folds")
+    else:
+        _lib.check(_lib.load().eegnet_frozen_step_folds_from(*args, ctypes.c_int(stage)),
+                   "eegnet_frozen_step_folds_from")
 
 
 def eval_fold_table(entries, device) -> torch.Tensor:

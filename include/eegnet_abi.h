@@ -160,6 +160,36 @@ int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_b
                        float* adam_state, int32_t* step, float lr, float beta1, float beta2, float eps,
                        float* loss, float* logits, void* ws, void* stream, int flags);
 
+/* Partial fine-tuning: the frozen-BatchNorm step that trains a suffix of the layers.  train_from names the
+ * first trainable module in network order; every module before it is frozen.  The flat parameter layout is
+ * in network order, so the trainable set is the suffix [off, param_count) of params / grads and of both
+ * halves of adam_state, with off = eegnet_trainable_offset(dims, train_from):
+ *   EEGNET_TRAIN_ALL               nothing frozen                                        off = 0
+ *   EEGNET_TRAIN_FROM_AGGREGATION  temporal.0, temporal.1, spatial frozen                aggregation.0.weight
+ *   EEGNET_TRAIN_FROM_BLOCK2       ... and aggregation.0 (gamma2, beta2)                 block_2.0.weight
+ *   EEGNET_TRAIN_FROM_CLASSIFIER   ... and block_2.0, block_2.1, block_2.2               classifier.weight
+ * (a cut at `spatial` is not offered: it still needs the whole block-1 backward but the temporal lag
+ * correlation.)  The backward of a trial stops where the trainable layers stop, so a later cut is cheaper.
+ *
+ * eegnet_frozen_step_from / eegnet_frozen_step_folds_from take the arguments of eegnet_frozen_step /
+ * eegnet_frozen_step_folds (same flags, same pointer checks, same workspace) and train_from:
+ *   - train_from = EEGNET_TRAIN_ALL is the existing call, bit for bit (the same kernels);
+ *   - otherwise grads[0 : off), params[0 : off) and both Adam moments of the prefix are never written;
+ *   - grads[off :), loss and logits are bit-identical to the full step on the same inputs; Adam runs on the
+ *     suffix alone and the step counter advances as in the full step;
+ *   - the content of ws before the call does not matter (as for the full step);
+ *   - a train_from outside 0..3 is EEGNET_EINVAL, wide dims (F1*D > 16) are rejected as by
+ *     eegnet_frozen_step.  All validation works without a GPU; capturable in a hipGraph.
+ * For the fold call train_from is shared by every fold. */
+enum { EEGNET_TRAIN_ALL = 0, EEGNET_TRAIN_FROM_AGGREGATION = 1,
+       EEGNET_TRAIN_FROM_BLOCK2 = 2, EEGNET_TRAIN_FROM_CLASSIFIER = 3 };
+int eegnet_trainable_offset(const eegnet_dims* dims, int train_from, int64_t* out);
+int eegnet_frozen_step_from(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,
+                            const float* dlogits, const int64_t* labels, const uint8_t* mask2,
+                            const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads,
+                            float* adam_state, int32_t* step, float lr, float beta1, float beta2, float eps,
+                            float* loss, float* logits, void* ws, void* stream, int flags, int train_from);
+
 /* bf16 batched eval-mode forward (BASELINE cfg5, EEGNet-16,4 at 64ch x 512):
  * the same function as eegnet_forward_eval (model.py:91-99 in .eval(), called at model.py:161/220,
  * ui.py:35) on bf16 input x [B,C,T] (16-byte aligned when T % 8 == 0), bf16 MFMA operands and fp32
@@ -261,6 +291,12 @@ int eegnet_frozen_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_f
                              int64_t row0, int64_t slot, uint64_t offset,
                              float lr, float beta1, float beta2, float eps,
                              int flags, void* stream);
+/* eegnet_frozen_step_folds training the suffix train_from of every fold (see eegnet_frozen_step_from):
+ * per fold bit-identical to eegnet_frozen_step_from with the same train_from on that fold alone. */
+int eegnet_frozen_step_folds_from(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds,
+                                  int64_t row0, int64_t slot, uint64_t offset,
+                                  float lr, float beta1, float beta2, float eps,
+                                  int flags, void* stream, int train_from);
 
 /* One model (fold) of a fold-indexed validation call.  Every pointer is a device pointer; an array of
  * these lives in DEVICE memory.  Nothing in it is written except through logits, ce, pred, loss and
