@@ -1,14 +1,18 @@
 """MI355X-native EEGNet train/infer step (drop-in for PraKesEy/EEGNetReplication's hot path).
 
 Public surface mirrors ``eegnet_repl.model``: ``EEGNet``, ``train``, ``evaluate_model``; ``saliency``
-and ``relevance_maps`` give the eval-mode input gradients the reference gets from plain autograd.
+and ``relevance_maps`` give the eval-mode input gradients the reference gets from plain autograd;
+``sliding_logits``, ``cropped_predict`` and ``evaluate_cropped`` classify every window of a continuous
+recording in place.
 The compute runs in ``libeegnet_hip.so`` (hand-written gfx950 HIP kernels, C-ABI in
 ``include/eegnet_abi.h``).
 """
 
 from .model import EEGNet, FusedTrainer, evaluate_model, relevance_maps, saliency, train  # noqa: F401
+from .model import cropped_predict, evaluate_cropped, sliding_logits, window_starts  # noqa: F401
 from .folds import FoldBatch, FrozenFoldBatch, evaluate_folds  # noqa: F401
 from .ops import Shape  # noqa: F401
 
-__all__ = ["EEGNet", "FoldBatch", "FrozenFoldBatch", "FusedTrainer", "Shape", "evaluate_folds", "evaluate_model",
-           "relevance_maps", "saliency", "train"]
+__all__ = ["EEGNet", "FoldBatch", "FrozenFoldBatch", "FusedTrainer", "Shape", "cropped_predict",
+           "evaluate_cropped", "evaluate_folds", "evaluate_model", "relevance_maps", "saliency", "sliding_logits",
+           "train", "window_starts"]

@@ -96,6 +96,11 @@ _SIGS = {
                                                      _vp, ctypes.c_int]),
     "eegnet_eval_folds": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int,
                                          ctypes.c_int64, _vp]),
+    "eegnet_window_count": (ctypes.c_int, [ctypes.POINTER(Dims), ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.POINTER(ctypes.c_int64)]),
+    "eegnet_forward_eval_windows": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int64,
+                                                   ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp,
+                                                   _vp]),
     "eegnet_eval_fold_bytes": (ctypes.c_size_t, []),
     "eegnet_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "eegnet_profile_collect": (ctypes.c_int, [ctypes.c_char_p, _vp, _vp, ctypes.c_int, _vp]),

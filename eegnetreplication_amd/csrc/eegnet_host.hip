@@ -334,6 +334,7 @@ static void set_attrs_shape() {
                           (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_CLS>})
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_eval_folds<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)k_infer_win<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 template <int K1>
@@ -1199,6 +1200,73 @@ int eegnet_eval_folds(const eegnet_dims* dims, int nfolds, const eegnet_eval_fol
         ec.chunk = 1;
     }
     return launch(KID_NONE, "k_eval_folds_reduce", k_eval_folds_reduce, dim3((unsigned)nfolds), dim3(NTER), 0, s, ec);
+}
+
+// W = (n_samples - T) / hop + 1 of a recording, with the checks both window entry points share
+static int window_count(const Geo& g, int64_t n_samples, int64_t hop, int64_t* W) {
+    if (hop < 1) return fail(EEGNET_EINVAL, "sliding windows: hop must be >= 1 (got %lld)", (long long)hop);
+    if (n_samples < g.T)
+        return fail(EEGNET_EINVAL, "sliding windows: n_samples = %lld is shorter than one window (T = %d)",
+                    (long long)n_samples, g.T);
+    *W = (n_samples - g.T) / hop + 1;
+    return 0;
+}
+
+int eegnet_window_count(const eegnet_dims* dims, int64_t n_samples, int64_t hop, int64_t* out) {
+    if (!dims) return fail(EEGNET_EINVAL, "dims is NULL");
+    eegnet_dims d = *dims;
+    d.B = 1;                                          // dims->B is ignored: the count is per recording
+    Geo g;
+    if (int r = make_geo(&d, &g, false)) return r;
+    if (!out) return fail(EEGNET_EINVAL, "out is NULL");
+    return window_count(g, n_samples, hop, out);
+}
+
+int eegnet_forward_eval_windows(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                                const float* rec, int64_t n_rec, int64_t n_samples, int64_t pitch, int64_t hop,
+                                float* logits, float* probs, int32_t* pred, void* stream) {
+    if (!dims) return fail(EEGNET_EINVAL, "dims is NULL");
+    eegnet_dims d = *dims;
+    d.B = 1;                                          // dims->B is ignored: n_rec and the window count size the call
+    Geo g;
+    if (int r = make_geo_narrow(&d, &g, "sliding windows")) return r;
+    if (g.XP != g.T) return fail(EEGNET_EINVAL, "sliding windows: x_pitch must be 0 or T (the rows' pitch is `pitch`)");
+    if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
+    if (int r = check_ptrs(rec, "rec", logits, "logits")) return r;
+    if (n_rec < 1) return fail(EEGNET_EINVAL, "sliding windows: n_rec must be >= 1 (got %lld)", (long long)n_rec);
+    int64_t W = 0;
+    if (int r = window_count(g, n_samples, hop, &W)) return r;
+    if (pitch < n_samples)
+        return fail(EEGNET_EINVAL, "sliding windows: pitch = %lld is below n_samples = %lld", (long long)pitch,
+                    (long long)n_samples);
+    // every window is one trial of the eval forward: the total must be a batch eegnet_forward_eval takes
+    const double total_d = (double)n_rec * (double)W;
+    if (total_d > 2147483647.0)
+        return fail(EEGNET_EINVAL, "sliding windows: n_rec * W = %.0f windows exceed the batch the eval forward takes",
+                    total_d);
+    d.B = (int)(n_rec * W);
+    if (make_geo(&d, &g)) {
+        const std::string why = g_err;
+        return fail(EEGNET_EINVAL, "sliding windows: n_rec * W = %d windows exceed the batch the eval forward takes (%s)",
+                    d.B, why.c_str());
+    }
+    WinCall wc;
+    wc.rec = rec;
+    wc.pitch = pitch;
+    wc.hop = hop;
+    wc.W = (int)W;
+    wc.total = d.B;
+    // 16-byte loads only when every window row starts 16-byte aligned
+    wc.vec = (g.T & 3) == 0 && (hop & 3) == 0 && (pitch & 3) == 0 && ((uintptr_t)rec & 15) == 0;
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    if (int r = dispatch_shape(g, [&](auto sh) {
+            return launch(KID_NONE, "k_infer_win", k_infer_win<SHAPE_OF(sh)>, dim3(g.grid), dim3(NTH), g.ldsI * 4, s, g,
+                          params, bn_buffers, wc, logits);
+        })) return r;
+    if (!probs && !pred) return 0;
+    return launch(KID_NONE, "k_win_reduce", k_win_reduce, dim3((unsigned)n_rec), dim3(NTWR), 0, s, logits, wc.W, probs,
+                  pred);
 }
 
 int eegnet_launch_grids(const eegnet_dims* dims, int fold_launch, int out[6]) {

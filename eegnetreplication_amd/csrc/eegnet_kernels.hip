@@ -42,6 +42,7 @@
 #include "eegnet_input_grad.hip"
 #include "eegnet_frozen.hip"
 #include "eegnet_eval_folds.hip"
+#include "eegnet_windows.hip"
 #include "eegnet_wide.hip"
 #include "eegnet_infer_bf16.hip"
 #include "eegnet_infer_bf16c.hip"

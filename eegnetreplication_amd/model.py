@@ -480,6 +480,74 @@ def relevance_maps(model, loader, method="gradxinput"):
 
 
 # ----------------------------------------------------------------------------------------------
+# sliding windows over continuous recordings (pseudo-online decoding, cropped evaluation)
+# ----------------------------------------------------------------------------------------------
+def window_starts(N, T, hop) -> torch.Tensor:
+    """Start sample of every T-sample window, ``hop`` samples apart, of a recording of N samples:
+    window w is samples [w hop, w hop + T); there are (N - T) // hop + 1 of them."""
+    N, T, hop = int(N), int(T), int(hop)
+    if hop < 1:
+        raise ValueError(f"hop must be >= 1 (got {hop})")
+    if N < T:
+        raise ValueError(f"a recording of {N} samples is shorter than one window (T = {T})")
+    return torch.arange(0, N - T + 1, hop, dtype=torch.int64)
+
+
+def _windows(model, rec, hop, reduce):
+    """ops.forward_eval_windows on a model: eval semantics whatever ``model.training`` is."""
+    require_device(rec, "EEGNet recording")
+    if rec.dtype != torch.float32:
+        raise RuntimeError(f"sliding windows expect a float32 recording (got {rec.dtype})")
+    if rec.dim() not in (2, 3) or rec.shape[-2] != model.C or rec.shape[-1] < model.T:
+        raise RuntimeError(f"expected a recording [{model.C}, N] or [R, {model.C}, N] with N >= {model.T}, "
+                           f"got {list(rec.shape)}")
+    flat = model.flat_parameters()
+    require_device(flat, "EEGNet parameters")
+    with torch.no_grad():
+        try:
+            return ops.forward_eval_windows(model.shape, flat, model.flat_bn_buffers(), rec.detach(), int(hop),
+                                            reduce=reduce)
+        except RuntimeError as e:
+            _not_supported(e)
+
+
+def sliding_logits(model, rec, hop):
+    """Logits of every T-sample window of continuous recordings, a decision every ``hop`` samples:
+    [R, W, 4] for ``rec`` [R, C, N] ([W, 4] for [C, N]), W = (N - T) // hop + 1, window w being samples
+    [w hop, w hop + T) (``window_starts``).  The recording is read in place (a contiguous tensor or a
+    time slice of one; no unfolded copy), and every row is bit-identical to ``model.eval()(window)``.
+    Always eval semantics (running statistics, no dropout), whatever ``model.training`` is, and that
+    mode is left untouched.  F1*D > 16 models raise NotImplementedError."""
+    return _windows(model, rec, hop, False)
+
+
+def cropped_predict(model, rec, hop):
+    """Cropped decoding of long trials: ``(probs, pred, logits)`` with logits as ``sliding_logits``,
+    probs [R, 4] the mean over a recording's crops of softmax(logits) (accumulated in float64 on the
+    device, in window order) and pred [R] int32 its argmax, the lowest class on a tie ([4] and a 0-d
+    tensor for a 2-D ``rec``).  Eval semantics; the mode is left untouched."""
+    logits, probs, pred = _windows(model, rec, hop, True)
+    return probs, pred, logits
+
+
+def evaluate_cropped(model, loader, hop) -> float:
+    """Accuracy in percent of the crop-averaged prediction (``cropped_predict``) over a loader of
+    ``([b, C, N], labels)`` batches of long trials: ``evaluate_model`` for cropped evaluation, with the
+    count kept on the device and one host sync at the end."""
+    device = _device()
+    model = model.to(device)
+    correct = torch.zeros((), dtype=torch.int64, device=device)
+    total = 0
+    for signals, labels in loader:
+        signals = signals.float().to(device, non_blocking=True)
+        labels = labels.to(device, non_blocking=True)
+        _, pred, _ = cropped_predict(model, signals, hop)
+        correct += (pred.long() == labels).sum()
+        total += labels.size(0)
+    return 100 * int(correct.item()) / total
+
+
+# ----------------------------------------------------------------------------------------------
 # train / evaluate_model  (model.py:101-227)
 # ----------------------------------------------------------------------------------------------
 def _device():

@@ -169,6 +169,53 @@ def forward_eval(shape: Shape, flat_params, bn_flat, x) -> torch.Tensor:
     return logits
 
 
+def window_count(shape: Shape, n_samples: int, hop: int) -> int:
+    """eegnet_window_count: the T-sample windows, ``hop`` samples apart, of a recording of ``n_samples``
+    samples -- (n_samples - T) // hop + 1.  Host-side only."""
+    out = ctypes.c_int64(0)
+    _lib.check(_lib.load().eegnet_window_count(ctypes.byref(shape.dims(1)), ctypes.c_int64(n_samples),
+                                               ctypes.c_int64(hop), ctypes.byref(out)), "eegnet_window_count")
+    return int(out.value)
+
+
+def forward_eval_windows(shape: Shape, flat_params, bn_flat, rec, hop: int, *, reduce=False):
+    """Eval-mode forward of every T-sample window of continuous recordings (eegnet_forward_eval_windows):
+    window w of a recording is its samples [w hop, w hop + T).  ``rec`` is [C, N] or [R, C, N] float32 on
+    the device and is read in place -- no unfolded copy -- when its last stride is 1 and its channel and
+    recording strides are ``pitch`` and ``C * pitch`` (a contiguous tensor, or a time slice of one);
+    anything else is made contiguous first.  Returns logits [R, W, 4] ([W, 4] for a 2-D ``rec``), each
+    row bit-identical to ``forward_eval`` on that window; with ``reduce=True`` ``(logits, probs, pred)``,
+    probs [R, 4] = the mean over a recording's windows of softmax(logits) (accumulated in float64) and
+    pred [R] int32 its argmax (``[4]`` and a 0-d tensor for a 2-D ``rec``)."""
+    require_device(rec, "rec")
+    if rec.dtype != torch.float32:
+        raise RuntimeError(f"forward_eval_windows expects float32 input (got {rec.dtype})")
+    if rec.dim() not in (2, 3) or rec.shape[-2] != shape.C:
+        raise RuntimeError(f"expected a recording [{shape.C}, N] or [R, {shape.C}, N], got {list(rec.shape)}")
+    squeeze = rec.dim() == 2
+    r3 = rec.unsqueeze(0) if squeeze else rec
+    R, C, N = r3.shape
+    pitch = r3.stride(1) if C > 1 else r3.stride(0) if R > 1 else N      # (a size-1 dim's stride says nothing)
+    in_place = r3.stride(2) == 1 and pitch >= N and (R <= 1 or r3.stride(0) == C * pitch)
+    if not in_place:
+        r3 = r3.contiguous()
+        pitch = N
+    W = window_count(shape, N, hop)                       # (raises on hop < 1 or N < T)
+    logits = torch.empty((R, W, NCLS), dtype=torch.float32, device=rec.device)
+    probs = torch.empty((R, NCLS), dtype=torch.float32, device=rec.device) if reduce else None
+    pred = torch.empty((R,), dtype=torch.int32, device=rec.device) if reduce else None
+    if R:
+        _lib.check(_lib.load().eegnet_forward_eval_windows(
+            ctypes.byref(shape.dims(1)), _ptr(flat_params), _ptr(bn_flat), _ptr(r3), ctypes.c_int64(R),
+            ctypes.c_int64(N), ctypes.c_int64(pitch), ctypes.c_int64(hop), _ptr(logits), _ptr(probs), _ptr(pred),
+            _stream()), "eegnet_forward_eval_windows")
+    if squeeze:
+        logits = logits[0]
+        if reduce:
+            probs, pred = probs[0], pred[0]
+    return (logits, probs, pred) if reduce else logits
+
+
 SEED_DLOGITS, SEED_LOGIT, SEED_CE = 0, 1, 2     # include/eegnet_abi.h EEGNET_SEED_*
 _SEED_KINDS = {"dlogits": SEED_DLOGITS, "logit": SEED_LOGIT, "ce": SEED_CE}
 

@@ -333,6 +333,28 @@ typedef struct eegnet_eval_fold {
 int eegnet_eval_folds(const eegnet_dims* dims, int nfolds, const eegnet_eval_fold* folds,
                       int64_t max_n, int batch, int64_t slot, void* stream);
 
+/* Sliding-window inference over continuous recordings, read in place (pseudo-online decoding, cropped
+ * evaluation).  `rec` holds n_rec recordings of dims->C channel rows: row (r, c) starts at
+ * rec + (r*C + c)*pitch and has n_samples valid floats, pitch >= n_samples (a time slice of a larger
+ * buffer is passed in place); rec may have any 4-byte alignment, and no byte outside
+ * [row start, row start + n_samples) of a row is read.  Window w of recording r is samples
+ * [w*hop, w*hop + T) of each of its rows, w < W = (n_samples - T)/hop + 1 (eegnet_window_count; host only).
+ *   logits [n_rec, W, 4]  required: logits[r, w] is bit-identical to eegnet_forward_eval on that window
+ *                         copied out as one [1, C, T] trial
+ *   probs  [n_rec, 4]     nullable, fp32: mean_w softmax(logits[r, w]), the softmax and the sum in fp64 in
+ *                         window-index order with a fixed reduction shape
+ *   pred   [n_rec]        nullable: the argmax of that fp64 mean, the lowest index on a tie (it does not
+ *                         need probs)
+ * One launch over all n_rec*W windows, and one more (a workgroup per recording) when probs or pred is
+ * asked for.  No atomics: the same inputs give the same bits.  dims->B is ignored; x_pitch must be 0 or
+ * T; hop >= 1, n_rec >= 1, n_samples >= T; n_rec*W must be a batch eegnet_forward_eval takes for these
+ * dims; F1*D <= 16 only.  No host synchronisation and no allocation: capturable in a hipGraph.  The
+ * validation needs no GPU. */
+int eegnet_window_count(const eegnet_dims* dims, int64_t n_samples, int64_t hop, int64_t* out);
+int eegnet_forward_eval_windows(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                                const float* rec, int64_t n_rec, int64_t n_samples, int64_t pitch,
+                                int64_t hop, float* logits, float* probs, int32_t* pred, void* stream);
+
 /* Per-trial BatchNorm-1 statistics of x that do not depend on the parameters: for each of the n
  * trials x[i] ([C][T] rows at dims->x_pitch), the lag sums of its zero-padded rows summed over the
  * channels G0[d] (d < K1), the window-0 sample sum, and the head / tail products and sums of the
