@@ -101,6 +101,11 @@ _SIGS = {
     "eegnet_forward_eval_windows": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int64,
                                                    ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp,
                                                    _vp]),
+    "eegnet_ems_chunk": (ctypes.c_int, []),
+    "eegnet_ems_scratch_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
+    "eegnet_ems": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,
+                                  ctypes.c_int64, ctypes.c_double, ctypes.c_int64, ctypes.c_double, _vp,
+                                  ctypes.c_int, _vp, _vp]),
     "eegnet_eval_fold_bytes": (ctypes.c_size_t, []),
     "eegnet_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "eegnet_profile_collect": (ctypes.c_int, [ctypes.c_char_p, _vp, _vp, ctypes.c_int, _vp]),

@@ -1132,6 +1132,19 @@ static void fold_grids(Geo* g) {
     g->grid = std::max(1, std::min(g->grid, (g->B + tpwC - 1) / tpwC));
 }
 
+// the three launches of eegnet_ems on rows of T: chunk aggregates, carries, output; scratch holds the
+// aggregates [n_rows][n_chunks][EMS_AGG], then the carries [n_rows][n_chunks][2]
+template <class T>
+static int ems_launch(const EmsCall& ec, const void* x, float* y, double* state, void* scratch, hipStream_t s) {
+    const dim3 grid((unsigned)(ec.n_rows * ec.n_chunks));
+    double* agg = (double*)scratch;
+    double* carry = agg + (size_t)ec.n_rows * ec.n_chunks * EMS_AGG;
+    if (int r = launch(KID_NONE, "k_ems_agg", k_ems_agg<T>, grid, dim3(EMS_NT), 0, s, ec, (const T*)x, agg)) return r;
+    if (int r = launch(KID_NONE, "k_ems_carry", k_ems_carry<T>, dim3((unsigned)ec.n_rows), dim3(EMS_NTC), 0, s, ec,
+                       (const T*)x, agg, carry, state)) return r;
+    return launch(KID_NONE, "k_ems_out", k_ems_out<T>, grid, dim3(EMS_NT), 0, s, ec, (const T*)x, carry, y);
+}
+
 extern "C" {
 
 int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
@@ -1267,6 +1280,74 @@ int eegnet_forward_eval_windows(const eegnet_dims* dims, const float* params, co
     if (!probs && !pred) return 0;
     return launch(KID_NONE, "k_win_reduce", k_win_reduce, dim3((unsigned)n_rec), dim3(NTWR), 0, s, logits, wc.W, probs,
                   pred);
+}
+
+// chunks per row and workgroups of an eegnet_ems call; the sizes are checked before anything is multiplied
+constexpr int64_t EMS_MAX_GRID = 2147483647;          // hipLaunchKernel's grid.x
+static int ems_sizes(int64_t n_rows, int64_t n_samples, int64_t* n_chunks) {
+    if (n_rows < 1) return fail(EEGNET_EINVAL, "eegnet_ems: n_rows must be >= 1 (got %lld)", (long long)n_rows);
+    if (n_samples < 1) return fail(EEGNET_EINVAL, "eegnet_ems: n_samples must be >= 1 (got %lld)", (long long)n_samples);
+    const int64_t nc = (n_samples - 1) / EMS_L + 1;
+    if (nc > EMS_MAX_GRID / n_rows)
+        return fail(EEGNET_EINVAL, "eegnet_ems: n_rows = %lld rows of %lld chunks (%d samples each) exceed the grid "
+                    "limit of %lld workgroups", (long long)n_rows, (long long)nc, EMS_L, (long long)EMS_MAX_GRID);
+    *n_chunks = nc;
+    return 0;
+}
+
+int eegnet_ems_chunk(void) { return EMS_L; }
+
+int eegnet_ems_scratch_bytes(int64_t n_rows, int64_t n_samples, size_t* out) {
+    int64_t nc = 0;
+    if (int r = ems_sizes(n_rows, n_samples, &nc)) return r;
+    if (!out) return fail(EEGNET_EINVAL, "out is NULL");
+    *out = (size_t)n_rows * (size_t)nc * (EMS_AGG + 2) * sizeof(double);      // aggregates, then carries
+    return 0;
+}
+
+int eegnet_ems(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, int64_t x_pitch, float* y,
+               int64_t y_pitch, double factor_new, int64_t init_block, double eps, double* state, int resume,
+               void* scratch, void* stream) {
+    if (int r = check_ptrs(x, "x", y, "y")) return r;
+    if (int r = check_ptrs(scratch, "scratch")) return r;
+    int64_t n_chunks = 0;
+    if (int r = ems_sizes(n_rows, n_samples, &n_chunks)) return r;
+    if (x_pitch < n_samples)
+        return fail(EEGNET_EINVAL, "eegnet_ems: x_pitch = %lld is below n_samples = %lld", (long long)x_pitch,
+                    (long long)n_samples);
+    if (y_pitch < n_samples)
+        return fail(EEGNET_EINVAL, "eegnet_ems: y_pitch = %lld is below n_samples = %lld", (long long)y_pitch,
+                    (long long)n_samples);
+    if (!(factor_new > 0.0 && factor_new < 1.0))
+        return fail(EEGNET_EINVAL, "eegnet_ems: factor_new must lie in (0, 1) (got %g)", factor_new);
+    if (!(eps >= 0.0)) return fail(EEGNET_EINVAL, "eegnet_ems: eps must be >= 0 (got %g)", eps);
+    if (resume) {
+        if (!state) return fail(EEGNET_EINVAL, "eegnet_ems: resume needs state");
+    } else if (init_block < 1) {
+        return fail(EEGNET_EINVAL, "eegnet_ems: init_block must be >= 1 (got %lld)", (long long)init_block);
+    }
+    if ((const void*)y == x) {
+        if (x_is_f64) return fail(EEGNET_EINVAL, "eegnet_ems: y may be x for fp32 input only");
+        if (y_pitch != x_pitch)
+            return fail(EEGNET_EINVAL, "eegnet_ems: y is x but y_pitch = %lld is not x_pitch = %lld", (long long)y_pitch,
+                        (long long)x_pitch);
+    }
+    const uintptr_t xa = x_is_f64 ? 7 : 3;
+    if (((uintptr_t)x & xa) || ((uintptr_t)y & 3) || ((uintptr_t)scratch & 7) || ((uintptr_t)state & 7))
+        return fail(EEGNET_EINVAL, "eegnet_ems: x, y, state and scratch must be aligned to their element size");
+    EmsCall ec;
+    ec.n_rows = n_rows;
+    ec.n = n_samples;
+    ec.n_chunks = n_chunks;
+    ec.x_pitch = x_pitch;
+    ec.y_pitch = y_pitch;
+    ec.a = factor_new;
+    ec.p = 1.0 - factor_new;
+    ec.eps = eps;
+    ec.init_n = resume ? 0 : std::min(init_block, n_samples);
+    ec.resume = resume ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    return x_is_f64 ? ems_launch<double>(ec, x, y, state, scratch, s) : ems_launch<float>(ec, x, y, state, scratch, s);
 }
 
 int eegnet_launch_grids(const eegnet_dims* dims, int fold_launch, int out[6]) {

@@ -72,7 +72,8 @@ def synthetic_session(subject: int, mode: str = "Train", n=TRIALS_PER_SESSION, C
     everywhere; each subject gets its own strength and spatial mixing, on top of 1/f noise.  The
     effect sizes (SYNTH_PARAMS) put per-subject test accuracy in the 40-100 % range (cross-subject
     mean 69 %, within-subject 86 %), so both protocols learn and neither comparison is saturated.
-    Trials are standardised per channel like the reference's exponential moving standardisation."""
+    Trials are standardised per channel and per trial, in place of the reference's exponential moving
+    standardisation of the whole recording (that one is ``preprocess.exponential_moving_standardize``)."""
     sess = 0 if mode == "Train" else 1
     rng = np.random.default_rng(1000 * subject + 17 * sess + 3)
     srng = np.random.default_rng(1000 * subject)          # subject-specific, session-independent

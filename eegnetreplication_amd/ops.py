@@ -216,6 +216,66 @@ def forward_eval_windows(shape: Shape, flat_params, bn_flat, rec, hop: int, *, r
     return (logits, probs, pred) if reduce else logits
 
 
+def ems_chunk() -> int:
+    """eegnet_ems_chunk: the samples of one chunk of the standardisation's scan.  Host-side only."""
+    return int(_lib.load().eegnet_ems_chunk())
+
+
+def _row_pitch(t: torch.Tensor):
+    """The element pitch of the rows of ``t`` [R, C, N] when they lie at one pitch (last stride 1, pitch >= N,
+    recording stride C * pitch), else None.  A size-1 dimension's stride says nothing."""
+    R, C, N = t.shape
+    pitch = t.stride(1) if C > 1 else t.stride(0) if R > 1 else N
+    if N > 1 and t.stride(2) != 1:
+        return None
+    if pitch < N or (C > 1 and R > 1 and t.stride(0) != C * pitch):
+        return None
+    return int(pitch)
+
+
+def ems(x, out=None, *, factor_new=1e-3, init_block=1000, eps=1e-10, state=None, resume=False):
+    """Exponential moving standardisation of continuous recordings (eegnet_ems): per row
+    m_t = (1-a) m_{t-1} + a x_t, v_t = (1-a) v_{t-1} + a (x_t - m_t)^2, y_t = (x_t - m_t) / sqrt(v_t + eps),
+    a = ``factor_new``, in float64 on the device, rounded to float32 once.  ``x`` is [R, C, N] float32 or
+    float64 on the device and is read in place when its rows lie at one pitch (a contiguous tensor or a time
+    slice of one); anything else is made contiguous first.  ``out``: a float32 [R, C, N] device tensor whose
+    rows lie at one pitch, to receive y -- ``x`` itself for an in-place call (float32) -- else a new
+    contiguous one.  ``state``: float64 [R * C, 2] = (mean, var) per row; it receives the final state, and
+    with ``resume`` the rows start from it instead of from their first ``init_block`` samples."""
+    require_device(x, "x")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"ems expects float32 or float64 input (got {x.dtype})")
+    if x.dim() != 3:
+        raise RuntimeError(f"expected recordings [R, C, N], got {list(x.shape)}")
+    R, C, N = x.shape
+    in_place = out is not None and out.data_ptr() == x.data_ptr()
+    xp = _row_pitch(x)
+    if xp is None:
+        if in_place:
+            raise ValueError("an in-place call needs rows at one pitch with a last stride of 1")
+        x, xp = x.contiguous(), N
+    if out is None:
+        out = torch.empty((R, C, N), dtype=torch.float32, device=x.device)
+    elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device or _row_pitch(out) is None:
+        raise ValueError(f"out must be a float32 {list(x.shape)} tensor on {x.device} whose rows lie at one pitch "
+                         f"(last stride 1)")
+    if state is not None and (state.dtype != torch.float64 or tuple(state.shape) != (R * C, 2)
+                              or not state.is_contiguous() or state.device != x.device):
+        raise ValueError(f"state must be a contiguous float64 [{R * C}, 2] tensor on {x.device}")
+    if R * C == 0 or N == 0:
+        return out
+    lib = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(lib.eegnet_ems_scratch_bytes(ctypes.c_int64(R * C), ctypes.c_int64(N), ctypes.byref(nbytes)),
+               "eegnet_ems_scratch_bytes")
+    scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.eegnet_ems(
+        _ptr(x), ctypes.c_int(x.dtype == torch.float64), ctypes.c_int64(R * C), ctypes.c_int64(N), ctypes.c_int64(xp),
+        _ptr(out), ctypes.c_int64(_row_pitch(out)), ctypes.c_double(factor_new), ctypes.c_int64(init_block),
+        ctypes.c_double(eps), _ptr(state), ctypes.c_int(1 if resume else 0), _ptr(scratch), _stream()), "eegnet_ems")
+    return out
+
+
 SEED_DLOGITS, SEED_LOGIT, SEED_CE = 0, 1, 2     # include/eegnet_abi.h EEGNET_SEED_*
 _SEED_KINDS = {"dlogits": SEED_DLOGITS, "logit": SEED_LOGIT, "ce": SEED_CE}
 

@@ -10,6 +10,7 @@
  *   the hot loop with bn.eval() on the three BatchNorm2d (fine-tuning) -> eegnet_frozen_step
  *   that fine-tuning loop for many models at once (per-subject fine-tuning, k folds each) -> eegnet_frozen_step_folds
  *   the per-epoch validation loop src/eegnet_repl/model.py:151-172, many folds at once -> eegnet_eval_folds
+ *   raw_exponential_moving_standardize  src/eegnet_repl/dataset.py:45-70 -> eegnet_ems
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer (hipMalloc / torch CUDA tensor) unless noted.  The library never
@@ -354,6 +355,34 @@ int eegnet_window_count(const eegnet_dims* dims, int64_t n_samples, int64_t hop,
 int eegnet_forward_eval_windows(const eegnet_dims* dims, const float* params, const float* bn_buffers,
                                 const float* rec, int64_t n_rec, int64_t n_samples, int64_t pitch,
                                 int64_t hop, float* logits, float* probs, int32_t* pred, void* stream);
+
+/* Exponential moving standardisation of continuous recordings: the reference's
+ * raw_exponential_moving_standardize (dataset.py:45-70), the step in front of eegnet_forward_eval_windows.
+ * Per row, with a = factor_new:
+ *     m_t = (1-a) m_{t-1} + a x_t,  v_t = (1-a) v_{t-1} + a (x_t - m_t)^2,  y_t = (x_t - m_t) / sqrt(v_t + eps)
+ * x holds n_rows rows (recordings x channels) of n_samples valid elements, fp32 or fp64 (x_is_f64), row i at
+ * x + i*x_pitch elements; y is fp32, row i at y + i*y_pitch; both pitches >= n_samples.  x may have any
+ * 4-byte (fp32) or 8-byte (fp64) alignment; no byte outside [row start, row start + n_samples) of a row is
+ * read and none outside y's valid samples is written.  y may be x itself (same pointer, same pitch, fp32
+ * input only); any other overlap of x and y is not supported.
+ *   resume = 0: (m, v) start as the mean and the population variance of the row's first
+ *               min(init_block, n_samples) samples (numpy's clamped slice)
+ *   resume = 1: (m, v) start from state[i] = (mean, var), which is then required: a recording fed block by
+ *               block (a pseudo-online decoder's standardiser)
+ * state, fp64 [n_rows][2], is nullable when not resuming; when non-NULL it receives every row's final (m, v).
+ * A blocked scan over time in three launches ordered by the stream alone (chunk aggregates, carries, output):
+ * all arithmetic fp64, y rounded to fp32 once, no atomics, no workgroup waits on another -- the same inputs
+ * give the same bits.  scratch: eegnet_ems_scratch_bytes(n_rows, n_samples) bytes, 8-byte aligned, content
+ * irrelevant.  eegnet_ems_chunk: the samples of one chunk of the scan (a compile-time constant).
+ * n_rows >= 1, n_samples >= 1, 0 < factor_new < 1, eps >= 0, init_block >= 1 when not resuming, and
+ * n_rows * ceil(n_samples / chunk) <= 2^31 - 1 workgroups.  No allocation and no host synchronisation:
+ * capturable in a hipGraph.  The validation needs no GPU; eegnet_ems_chunk and eegnet_ems_scratch_bytes are
+ * host only. */
+int eegnet_ems_chunk(void);
+int eegnet_ems_scratch_bytes(int64_t n_rows, int64_t n_samples, size_t* out);
+int eegnet_ems(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, int64_t x_pitch,
+               float* y, int64_t y_pitch, double factor_new, int64_t init_block, double eps,
+               double* state, int resume, void* scratch, void* stream);
 
 /* Per-trial BatchNorm-1 statistics of x that do not depend on the parameters: for each of the n
  * trials x[i] ([C][T] rows at dims->x_pitch), the lag sums of its zero-padded rows summed over the
