@@ -97,26 +97,19 @@ struct Geo {
     int XP;              // x row pitch (floats between channel rows; T unless eegnet_dims.x_pitch)
 };
 
-// Compile-time cfg5 geometry (EEGNet-16,4 at 64ch x 512, K1 = 32): the shape fields make_geo computes
-// for those dims (everything but B, the grids and the run-time keys / pointers).  The host launches
-// the SPEC instantiations of the wide kernels only when the run-time geometry matches these field for
-// field (eegnet_host.hip same_shape_w5), so a specialisation cannot disagree with the generic path;
-// with the bounds, strides and offsets constant the kernels fold their index arithmetic and unroll
-// (the bf16 eval kernel's kGeoCfg5 does the same, eegnet_infer_bf16.hip).
-#define EEG_SHAPE_W5(X)                                                                             \
-    X(C, 64) X(T, 512) X(F1, 16) X(D, 4) X(F2, 64) X(K1, 32) X(P, 15) X(R, 16) X(T1, 128) X(T2, 16)  \
-    X(NF, 1024) X(LP, 16) X(RS, 548) X(TQ, 128) X(NT16, 32) X(RS2, 144) X(CK, 64)                   \
-    X(NCT, 4) X(NKG, 32) X(nH, 136) X(nTl, 120) X(nedge, 287) X(o_w1, 0) X(o_g1, 512) X(o_b1, 528)   \
-    X(o_ws, 544) X(o_g2, 4640) X(o_b2, 4704) X(o_w2, 4768) X(o_W3, 5792) X(o_g3, 9888) X(o_b3, 9952) \
-    X(o_Wfc, 10016) X(o_bfc, 14112) X(nparam, 14116) X(nA, 448) X(nB, 128) X(nC, 4229) X(nD, 5248)    \
-    X(nE, 6272) X(QR, 64) X(wide, 1) X(NOC, 4) X(CPC, 16) X(F2P, 64) X(RB, 144) X(splitC, 1)         \
-    X(splitD, 1) X(splitE, 1) X(ldsWA, 36656) X(ldsWB, 0) X(ldsWB2, 19712) X(ldsWC, 10528)           \
-    X(ldsWD, 37952) X(ldsWE, 29504) X(ldsWI, 37760)
-__host__ __device__ __forceinline__ void shape_w5(Geo& g) {
-#define EEG_SET_(f, v) g.f = v;
-    EEG_SHAPE_W5(EEG_SET_)
-#undef EEG_SET_
-}
+// Compile-time cfg5 geometry (EEGNet-16,4 at 64ch x 512, K1 = 32).  The SPEC instantiations of the wide
+// kernels replace these fields of their run-time Geo -- the shape fields the wide kernels read: everything
+// but B, the grids and the run-time keys / pointers -- with the constants of kGeoW5, which the host's own
+// geometry function computes for those dims at compile time (shape_w5, eegnet_geometry.h), so a
+// specialisation cannot disagree with the generic path; with the bounds, strides and offsets constant the
+// kernels fold their index arithmetic and unroll.  The host launches them for exactly those dims.
+#define EEG_FIELDS_W5(X)                                                                              \
+    X(C) X(T) X(F1) X(D) X(F2) X(K1) X(P) X(R) X(T1) X(T2) X(NF) X(LP) X(RS) X(TQ) X(NT16) X(RS2) X(CK)  \
+    X(NCT) X(NKG) X(nH) X(nTl) X(nedge) X(o_w1) X(o_g1) X(o_b1) X(o_ws) X(o_g2) X(o_b2) X(o_w2) X(o_W3) \
+    X(o_g3) X(o_b3) X(o_Wfc) X(o_bfc) X(nparam) X(nA) X(nB) X(nC) X(nD) X(nE) X(QR) X(wide) X(NOC)      \
+    X(CPC) X(F2P) X(RB) X(splitC) X(splitD) X(splitE) X(ldsWA) X(ldsWB) X(ldsWB2) X(ldsWC) X(ldsWD)    \
+    X(ldsWE) X(ldsWI)
+__host__ __device__ __forceinline__ void shape_w5(Geo& g);
 template <bool SPEC>
 __device__ __forceinline__ Geo geo_w(const Geo& gin) {
     Geo g = gin;

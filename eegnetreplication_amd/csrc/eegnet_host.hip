@@ -17,10 +17,6 @@ static int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-// dynamic LDS per workgroup: 160 KiB less a little room for the static LDS of the traced build
-constexpr int LDS_MAX = 160 * 1024 - 256;
-
-static inline int rup(int a, int m) { return (a + m - 1) / m * m; }
 static inline size_t rupz(size_t a, size_t m) { return (a + m - 1) / m * m; }
 
 constexpr size_t CNT_BYTES = (size_t)TK_COUNT * NCNT * TKS * 4;     // a multiple of 16
@@ -43,8 +39,6 @@ static int device_cus() {
 
 static unsigned long long* g_trace_buf = nullptr;     // eegnet_trace_enable
 
-static int make_geo_wide(Geo* g, bool launch);
-
 // The shipped library reads no environment: kernel choice and grids are functions of the dims alone.
 // The F2 <= 16 step runs passes C / D as k_pass_c (one trial per wave) and k_pass_dr (the row-layout
 // kernel on the streaming grid, eegnet_passes.hip).  The build switches that once selected other
@@ -52,165 +46,79 @@ static int make_geo_wide(Geo* g, bool launch);
 // multipliers, the whole-trial bf16 eval kernel at cfg5 -- lost their measurements
 // and are gone; commit d0e7be7 is the last that contains them.
 
-// the compile-time shape of the narrow passes (dispatch_shape) whose x loads honour a row pitch: 22 x 257
-// (the recordings), whose 257-float rows are not 16-byte units; 22 x 256 rows already are, and its
-// kernels take the pitch as the compile-time T (EEG_XP)
-static bool x_pitch_shape(const eegnet_dims& d) {
-    return d.K1 == 32 && d.C == 22 && d.T == 257 && d.F1 == 8 && d.D == 2;
-}
-
-static int make_geo(const eegnet_dims* d, Geo* g, bool launch = true) {
+// the dims every entry point takes; nothing is computed from dims that fail here
+static int check_dims(const eegnet_dims* d) {
     if (!d) return fail(EEGNET_EINVAL, "dims is NULL");
-    memset(g, 0, sizeof(*g));
-    g->trace = g_trace_buf;
-    g->B = d->B; g->C = d->C; g->T = d->T; g->F1 = d->F1; g->D = d->D; g->K1 = d->K1;
-    g->Bn = d->B;
-    g->F2 = d->F1 * d->D;
-    if (g->B < 1) return fail(EEGNET_EINVAL, "B must be >= 1 (got %d)", g->B);
-    if (g->K1 != 32 && g->K1 != 64) return fail(EEGNET_EINVAL, "K1 must be 32 or 64 (got %d)", g->K1);
-    if (g->C < 1 || g->C > 64) return fail(EEGNET_EINVAL, "C must be in [1,64] (got %d)", g->C);
-    if (g->F1 < 1 || g->D < 1 || g->F2 > 64 || (g->F2 & 3))
-        return fail(EEGNET_EINVAL, "F1*D must be a multiple of 4 in [4,64] (got F1=%d D=%d)", g->F1, g->D);
-    if (g->T < 32 || g->T < g->K1 || g->T > 1024)
-        return fail(EEGNET_EINVAL, "T must be in [max(32,K1), 1024] (got %d)", g->T);
-    g->XP = d->x_pitch ? d->x_pitch : g->T;
-    if (g->XP != g->T && !(x_pitch_shape(*d) && (g->XP & 3) == 0 && g->XP > g->T))
+    const int F2 = d->F1 * d->D;
+    if (d->B < 1) return fail(EEGNET_EINVAL, "B must be >= 1 (got %d)", d->B);
+    if (d->K1 != 32 && d->K1 != 64) return fail(EEGNET_EINVAL, "K1 must be 32 or 64 (got %d)", d->K1);
+    if (d->C < 1 || d->C > 64) return fail(EEGNET_EINVAL, "C must be in [1,64] (got %d)", d->C);
+    if (d->F1 < 1 || d->D < 1 || F2 > 64 || (F2 & 3))
+        return fail(EEGNET_EINVAL, "F1*D must be a multiple of 4 in [4,64] (got F1=%d D=%d)", d->F1, d->D);
+    if (d->T < 32 || d->T < d->K1 || d->T > 1024)
+        return fail(EEGNET_EINVAL, "T must be in [max(32,K1), 1024] (got %d)", d->T);
+    const int XP = d->x_pitch ? d->x_pitch : d->T;
+    if (XP != d->T && !(x_pitch_shape(model_dims(*d)) && (XP & 3) == 0 && XP > d->T))
         return fail(EEGNET_EINVAL, "x_pitch %d: only the 22 x 257 EEGNet-8,2 (K1 = 32) training kernels take "
-                    "a row pitch, a multiple of 4 above T (eegnet_x_pitch)", g->XP);
-    g->P = (g->K1 - 1) / 2; g->R = g->K1 - 1 - g->P;
-    g->T1 = g->T / 4; g->T2 = g->T1 / 8; g->NF = g->F2 * g->T2;
-    g->LP = (g->R + 3) & ~3;
-    g->TQ = (g->T + 3) / 4; g->NT16 = (g->T + 15) / 16; g->NKG = g->NT16;
-    g->RS = row_stride(g->K1, g->T);
-    g->RS2 = rup(LP2 + g->T1 + 8, 4);
-    g->CK = rup(g->C, 4); g->NCT = (g->C + 15) / 16;
-    g->nH = g->R * (g->R + 1) / 2;
-    g->nTl = g->P * (g->P + 1) / 2;
-    g->nedge = g->nH + g->nTl + g->R + g->P;
-    g->p = d->p_drop; g->eps = d->bn_eps; g->mom = d->bn_momentum;
-    if (!(g->p >= 0.f && g->p <= 1.f)) return fail(EEGNET_EINVAL, "p_drop must be in [0,1]");
-    g->scale = g->p < 1.f ? 1.f / (1.f - g->p) : 0.f;
-    int o = 0;
-    g->o_w1 = o; o += g->F1 * g->K1;
-    g->o_g1 = o; o += g->F1;
-    g->o_b1 = o; o += g->F1;
-    g->o_ws = o; o += g->F2 * g->C;
-    g->o_g2 = o; o += g->F2;
-    g->o_b2 = o; o += g->F2;
-    g->o_w2 = o; o += g->F2 * 16;
-    g->o_W3 = o; o += g->F2 * g->F2;
-    g->o_g3 = o; o += g->F2;
-    g->o_b3 = o; o += g->F2;
-    g->o_Wfc = o; o += NCLS * g->NF;
-    g->o_bfc = o; o += NCLS;
-    g->nparam = o;
-    if (g->NF < 1) return fail(EEGNET_EINVAL, "T//32 must be >= 1");
-    g->nA = g->K1 + 1 + g->nedge + 2 * g->F2;
-    g->nB = 2 * g->F2;
-    g->nC = NCLS * g->NF + NCLS + 2 * g->F2 + 1;
-    g->nD = g->F2 * g->F2 + 18 * g->F2;
-    g->QR = (g->F2 <= F2MAX && g->D == 2) ? g->F1 : g->F2;
-    g->nE = g->QR * g->K1 + g->F2 * g->C + 2 * g->F2;
-    g->grid = std::min(g->B, device_cus());             // pass C, infer
-    g->gridS = std::min(g->B, device_cus() * WGPC);     // streaming passes A, B, D, E
-    g->gridA = g->gridE = g->gridS;
-    const int rows1 = g->C * g->RS;                   // x rows (one buffer)
-    const int nf4 = rup(g->NF, 4);
-    const bool spec = g->C == 22 && (g->T == 256 || g->T == 257) && g->F1 == 8 && g->D == 2 && g->K1 == 32;   // dispatch_shape
-    // compile-time shapes: two x buffers, and two xstat-row slots (fold launches, eegnet_fold.xstat)
-    g->ldsA = (spec ? 2 : 1) * rows1 + g->F2 * g->RS + NWB * (g->K1 + 1) + (spec ? 2 * rup(g->K1 + 1 + g->nedge, 4) : 0);
-    g->ldsB = 3 * g->F2 * g->RS2 + F2MAX * (K2 + F2MAX);
-    // pass C: one trial stream per wave, each with its own row of head features
-    const int pwC = nf4;
-    g->nwC = std::max(1, std::min(spec ? NWAVE : NTHS / 64, (LDS_MAX / 4 - 4 * F2MAX) / pwC));
-    g->ldsC = std::max(g->nwC * pwC + 4 * F2MAX, g->nwC * g->nC);   // Hs rows + the BN3 constant table
-    g->ldsD = std::max(dr_lds_floats(spec ? 1 : MAXT1Q), dr_tail_floats(spec));     // k_pass_dr
-    g->ldsE = std::max((2 * g->F2 + g->C) * g->RS + rup(g->F2 * g->T1, 4) + 8 * g->F2,
-                       NWB * 256 * (1 + (15 + g->K1 - 1) / 16 + 1));   // after the loop: dws, Cq tiles
-    // the whole-trial kernels carve trial_lds (eegnet_trial.hip): ldsI is its plain plan without the logits
-    // (k_infer; k_eval_folds launches with ldsI + NCLS), ldsX its PLANE plan with them (k_infer_dx, k_frozen;
-    // checked by check_lds_x alone)
-    g->ldsI = trial_lds(g->C, g->F2, g->RS, g->RS2, g->NF, false).Lg;
-    g->ldsX = trial_lds(g->C, g->F2, g->RS, g->RS2, g->NF, true).n;
-    // the reduction tail and finalize reuse each pass kernel's LDS (doubles = 2 floats)
-    auto tail = [](int ncols, int fin) { return 2 * (tail_s_doubles(ncols) + std::max(tail_scratch_doubles(ncols), fin)); };
-    g->ldsA = std::max(g->ldsA, tail(g->nA, fin1_scratch_doubles(g->K1, g->F1, g->F2, g->C)));
-    g->ldsB = std::max(g->ldsB, tail(g->nB, 0));
-    g->ldsC = std::max(g->ldsC, tail(g->nC, 0));
-    g->ldsD = std::max(g->ldsD, tail(g->nD, 0));
-    g->ldsE = std::max(g->ldsE, tail(g->nE, fin5_scratch_doubles(g->K1, g->F1, g->o_g2)));
-    g->wide = g->F2 > F2MAX ? 1 : 0;
-    if (g->wide) return make_geo_wide(g, launch);
-    if (launch) {
-        if (g->C * g->T > NTH * MAXPF)
-            return fail(EEGNET_EINVAL, "C*T = %d exceeds the %d-float prefetch of one trial", g->C * g->T,
-                        NTH * MAXPF);
-        if (g->T1 > 64 * MAXT1Q) return fail(EEGNET_EINVAL, "T/4 > %d", 64 * MAXT1Q);
-        if (g->F2 * g->T1 > 4 * NTH) return fail(EEGNET_EINVAL, "F2*(T/4) > %d", 4 * NTH);
-        if ((double)g->B * g->F2 * g->T1 >= 4294967296.0)
-            return fail(EEGNET_EINVAL, "B*F2*(T/4) must stay below 2^32 (dropout / mask indices)");
-        if (g->NF > 64 * MAXNFQ) return fail(EEGNET_EINVAL, "F2*(T/32) = %d > %d", g->NF, 64 * MAXNFQ);
-        if (g->nparam > APT * NTB) return fail(EEGNET_EINVAL, "%d parameters > %d", g->nparam, APT * NTB);
-        const int lmax = std::max(std::max(std::max(g->ldsA, g->ldsB), std::max(g->ldsC, g->ldsD)),
-                                  std::max(g->ldsE, g->ldsI));
-        if (lmax * 4 > LDS_MAX) return fail(EEGNET_EINVAL, "dims need %d B of LDS (> %d)", lmax * 4, LDS_MAX);
-    }
+                    "a row pitch, a multiple of 4 above T (eegnet_x_pitch)", XP);
+    if (!(d->p_drop >= 0.f && d->p_drop <= 1.f)) return fail(EEGNET_EINVAL, "p_drop must be in [0,1]");
+    if (F2 * (d->T / 32) < 1) return fail(EEGNET_EINVAL, "T//32 must be >= 1");
     return 0;
 }
 
-// F2 > 16: o-chunked streaming passes and whole-trial block-2 passes (eegnet_wide.hip)
-static int make_geo_wide(Geo* g, bool launch) {
-    const int cus = device_cus();
-    g->NOC = (g->F2 + 15) / 16;
-    g->CPC = (g->C + g->NOC - 1) / g->NOC;
-    g->F2P = g->F2 <= 32 ? 32 : 64;
-    g->RB = rb_stride(g->T1);
-    // streaming grid: one 1024-thread workgroup per CU, NOC per trial range; a multiple of 8 * NOC
-    // when it can be (the chunk workgroups of a range then share an XCD)
-    int G = std::min(g->B * g->NOC, cus);
-    G = std::max(g->NOC, G / g->NOC * g->NOC);
-    if (G >= 8 * g->NOC) G = G / (8 * g->NOC) * (8 * g->NOC);
-    g->gridS = G;
-    g->gridA = g->gridE = G;
-    g->grid = std::min(g->B, cus);                      // block-2 passes and the eval forward
-    // partial rows wider than this reduce in k_coltail (column-parallel) instead of in-kernel
-    g->splitC = g->nC > SPLIT_COLS; g->splitD = g->nD > SPLIT_COLS; g->splitE = g->nE > SPLIT_COLS;
-    const int nf4 = rup(g->NF, 4);
-    auto tailw = [](int ncols, int fin) { return 2 * (tail_s_doubles(ncols) + fin); };
-    const int awl = KSW * 64;                               // spatial GEMM fragment table
-    // after the loop pass A's Gram tiles [NWW][16][16 NWT] reuse the slice / s rows when they fit
-    const int cgw = NWW * 256 * ((15 + g->K1 - 1) / 16 + 1);
-    // the cfg5 shape (k_wpass_a's SPEC instantiation) double-buffers the slice and the s rows
-    const bool w5 = g->C == 64 && g->T == 512 && g->F1 == 16 && g->D == 4 && g->K1 == 32;
-    const int baseA = (w5 ? 2 : 1) * (g->CPC + 16) * g->RS + NWW * (g->K1 + 1) + 2 * NWW + awl;
-    g->ldsWA = std::max(baseA + ((g->CPC + 16) * g->RS >= cgw ? 0 : cgw),
-                        tailw(g->nA, std::max(NTH, fin1_scratch_doubles(g->K1, g->F1, g->F2, g->C))));
-    g->ldsWB = 0;                                           // k_wpass_b: registers only (v plane)
-    const int b2 = 2 * g->F2P * g->RB + g->F2P * K2 + g->F2P * (g->F2P + 1);   // D2, Q, w2, W3 tables
-    // the whole-trial block-2 passes (k_wpass_b2 / c / d) at NWB2 waves
-    const int TQ1 = (g->T1 + 3) / 4;
-    g->ldsWB2 = std::max(b2 + NWB2 * 2 * 16, tailw(g->nB, 0));
-    g->ldsWC = std::max(nf4 + NWB2 * 4 + NWB2 * 2 * 16 + g->F2P * g->RB, tailw(g->nC, 0));    // H | sums | XH
-    g->ldsWD = std::max(b2 + g->F2P * g->RB + nf4 + 2 * g->F2 * TQ1, tailw(g->nD, 0));
-    // the cfg5 (SPEC) k_wpass_b2 keeps its W3 fragments in registers instead of an LDS table, and it and
-    // k_wpass_c stay within 128 VGPRs: two 8-wave workgroups per CU, two trials each at B = 1024, so one
-    // workgroup's barriers overlap the other's work
-    g->gridW2 = w5 ? std::min(g->B, 2 * cus) : g->grid;
-    if (w5) g->ldsWB2 = std::max(g->ldsWB2 - g->F2P * (g->F2P + 1), tailw(g->nB, 0));
-    // s rows, dy / e rows x 2 (alternate trials), dp2 rows, coefficient table
-    g->ldsWE = std::max(std::max(3 * 16 * g->RS + rup(16 * g->T1, 4) + 8 * 16 + awl, NWW * 256 + 32 + NWW * 256 * ((15 + g->K1 - 1) / 16 + 1)),
-                        tailw(g->nE, fin5_scratch_doubles(g->K1, g->F1, g->o_g2)));
-    g->ldsWI = 16 * g->RS + b2 + nf4 + 4 * g->F2P + g->NOC * awl;
-    if (!launch) return 0;
-    if (g->C > 4 * KSW) return fail(EEGNET_EINVAL, "C = %d > %d", g->C, 4 * KSW);
-    if (g->T1 > 16 * NTTW * (NWB2 / 4)) return fail(EEGNET_EINVAL, "T/4 = %d > %d", g->T1, 16 * NTTW * (NWB2 / 4));
-    if (g->NF > MAXNFW * NTB2) return fail(EEGNET_EINVAL, "F2*(T/32) = %d > %d", g->NF, MAXNFW * NTB2);
-    if ((double)g->B * g->F2 * g->T1 >= 4294967296.0)
-        return fail(EEGNET_EINVAL, "B*F2*(T/4) must stay below 2^32 (dropout / mask indices)");
-    const int lmax = std::max(std::max(std::max(g->ldsWA, g->ldsWB), std::max(g->ldsWB2, g->ldsWC)),
-                              std::max(std::max(g->ldsWD, g->ldsWE), g->ldsWI));
+// what the launches of a geometry's kernels can take: prefetch registers, per-thread tables, 32-bit
+// indices, LDS
+static int check_launch(const Geo& g) {
+    if (g.wide) {
+        if (g.C > 4 * KSW) return fail(EEGNET_EINVAL, "C = %d > %d", g.C, 4 * KSW);
+        if (g.T1 > 16 * NTTW * (NWB2 / 4)) return fail(EEGNET_EINVAL, "T/4 = %d > %d", g.T1, 16 * NTTW * (NWB2 / 4));
+        if (g.NF > MAXNFW * NTB2) return fail(EEGNET_EINVAL, "F2*(T/32) = %d > %d", g.NF, MAXNFW * NTB2);
+        if ((double)g.B * g.F2 * g.T1 >= 4294967296.0)
+            return fail(EEGNET_EINVAL, "B*F2*(T/4) must stay below 2^32 (dropout / mask indices)");
+    } else {
+        if (g.C * g.T > NTH * MAXPF)
+            return fail(EEGNET_EINVAL, "C*T = %d exceeds the %d-float prefetch of one trial", g.C * g.T, NTH * MAXPF);
+        if (g.T1 > 64 * MAXT1Q) return fail(EEGNET_EINVAL, "T/4 > %d", 64 * MAXT1Q);
+        if (g.F2 * g.T1 > 4 * NTH) return fail(EEGNET_EINVAL, "F2*(T/4) > %d", 4 * NTH);
+        if ((double)g.B * g.F2 * g.T1 >= 4294967296.0)
+            return fail(EEGNET_EINVAL, "B*F2*(T/4) must stay below 2^32 (dropout / mask indices)");
+        if (g.NF > 64 * MAXNFQ) return fail(EEGNET_EINVAL, "F2*(T/32) = %d > %d", g.NF, 64 * MAXNFQ);
+        if (g.nparam > APT * NTB) return fail(EEGNET_EINVAL, "%d parameters > %d", g.nparam, APT * NTB);
+    }
+    const int lmax = g.wide ? std::max({g.ldsWA, g.ldsWB, g.ldsWB2, g.ldsWC, g.ldsWD, g.ldsWE, g.ldsWI})
+                            : std::max({g.ldsA, g.ldsB, g.ldsC, g.ldsD, g.ldsE, g.ldsI});
     if (lmax * 4 > LDS_MAX) return fail(EEGNET_EINVAL, "dims need %d B of LDS (> %d)", lmax * 4, LDS_MAX);
     return 0;
+}
+
+// Geometry of a call: the dims checked, the shape fields by geo_shape (eegnet_geometry.h: the function the
+// compile-time geometries are values of), then what the call and the device add -- the batch, the dropout
+// and BatchNorm arguments, the grids -- and, with `launch`, the launch limits.
+static int make_geo(const eegnet_dims* d, Geo* g, bool launch = true) {
+    if (int r = check_dims(d)) return r;
+    *g = geo_shape(model_dims(*d));
+    g->trace = g_trace_buf;
+    g->B = g->Bn = d->B;
+    g->XP = d->x_pitch ? d->x_pitch : g->T;
+    g->p = d->p_drop; g->eps = d->bn_eps; g->mom = d->bn_momentum;
+    g->scale = g->p < 1.f ? 1.f / (1.f - g->p) : 0.f;
+    const int cus = device_cus();
+    g->grid = std::min(g->B, cus);                      // pass C, the block-2 passes, the eval forward
+    if (g->wide) {
+        // streaming grid: one 1024-thread workgroup per CU, NOC per trial range; a multiple of 8 * NOC
+        // when it can be (the chunk workgroups of a range then share an XCD)
+        int G = std::min(g->B * g->NOC, cus);
+        G = std::max(g->NOC, G / g->NOC * g->NOC);
+        if (G >= 8 * g->NOC) G = G / (8 * g->NOC) * (8 * g->NOC);
+        g->gridS = G;
+        // cfg5: two 8-wave workgroups of k_wpass_b2 / c per CU, two trials each at B = 1024, so one
+        // workgroup's barriers overlap the other's work
+        g->gridW2 = is_cfg5(model_dims(*g)) ? std::min(g->B, 2 * cus) : g->grid;
+    } else {
+        g->gridS = std::min(g->B, cus * WGPC);          // streaming passes A, B, D, E
+    }
+    g->gridA = g->gridE = g->gridS;
+    return launch ? check_launch(*g) : 0;
 }
 
 static WsLayout make_layout(const Geo& g) {
@@ -337,6 +245,9 @@ static void set_attrs_shape() {
     hipFuncSetAttribute((const void*)k_infer_win<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
+template <class... S>
+static void set_attrs_shapes(Shapes<S...>) { (..., set_attrs_shape<S::K1, S::CC, S::TT, S::FF>()); }
+
 template <int K1>
 static void set_attrs_wide() {
     for (const void* f : {(const void*)k_wpass_a<K1>, (const void*)k_wpass_b<K1>, (const void*)k_wpass_e<K1>,
@@ -367,23 +278,18 @@ static void ensure_attrs() {
     set_attrs_shape<64, 0, 0, 0>();
     hipFuncSetAttribute((const void*)k_xstats<32>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     hipFuncSetAttribute((const void*)k_xstats<64>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    set_attrs_shape<32, 22, 256, 16>();
-    set_attrs_shape<32, 22, 257, 16>();
+    set_attrs_shapes(NarrowShapes{});
     g_attr_done = true;
 }
 
-// The one shape switch: f(Shape<K1, CC, TT, FF>{}) for the compile-time shape specialisations (the
-// benchmark and real-data configurations), for any other shape the runtime-shape instantiation
+// The one shape switch: f(Shape<K1, CC, TT, FF>{}) for the compile-time shape specialisations
+// (NarrowShapes, eegnet_geometry.h), for any other shape the runtime-shape instantiation
 // (CC = TT = FF = 0) of its K1.  The wide kernels take K1 alone.
-template <int K1_, int CC_, int TT_, int FF_>
-struct Shape { static constexpr int K1 = K1_, CC = CC_, TT = TT_, FF = FF_; };
 #define SHAPE_OF(sh) decltype(sh)::K1, decltype(sh)::CC, decltype(sh)::TT, decltype(sh)::FF
 template <class F>
 static int dispatch_shape(const Geo& g, F&& f) {
-    if (g.K1 == 32 && g.C == 22 && g.F1 == 8 && g.D == 2) {
-        if (g.T == 256) return f(Shape<32, 22, 256, 16>{});
-        if (g.T == 257) return f(Shape<32, 22, 257, 16>{});
-    }
+    int r = 0;
+    if (NarrowShapes::any([&](auto sh) { return has_shape(model_dims(g), sh) && (r = f(sh), true); })) return r;
     return g.K1 == 32 ? f(Shape<32, 0, 0, 0>{}) : f(Shape<64, 0, 0, 0>{});
 }
 
@@ -416,14 +322,8 @@ static void attach_adam(FinArgs* fe, float* params, const FinArgs& adam) {
     fe->lr = adam.lr; fe->b1 = adam.b1; fe->b2 = adam.b2; fe->eps = adam.eps;
 }
 
-// the run-time geometry has the compile-time cfg5 shape (eegnet_common.h EEG_SHAPE_W5): launch the
-// SPEC instantiations of the wide kernels
-static bool same_shape_w5(const Geo& g) {
-#define EEG_EQ_(f, v) && g.f == v
-    return true EEG_SHAPE_W5(EEG_EQ_);
-#undef EEG_EQ_
-}
-static bool spec_w5(const Geo& g) { return g.K1 == 32 && same_shape_w5(g); }
+// the dims the SPEC instantiations of the wide kernels are compiled for (kGeoW5, eegnet_geometry.h)
+static bool spec_w5(const Geo& g) { return is_cfg5(model_dims(g)); }
 
 // k_wpass_b keeps nothing in LDS and needs 38 VGPRs at cfg5: two 16-wave workgroups per CU (elementwise,
 // so the grid does not touch the numerics)
@@ -555,66 +455,16 @@ static int run_backward(const Geo& g, const WsLayout& L, char* ws, float* params
 static float* g_bf16_dbg = nullptr;     // eegnet_debug_bf16 (debug builds only)
 
 static int make_geo_bf16(const eegnet_dims* d, GeoI* g) {
-    Geo q;
-    if (int r = make_geo(d, &q, false)) return r;
-    memset(g, 0, sizeof(*g));
-    g->B = q.B; g->C = q.C; g->T = q.T; g->F1 = q.F1; g->D = q.D; g->F2 = q.F2; g->K1 = q.K1; g->P = q.P;
-    g->eps = q.eps;
-    g->o_w1 = q.o_w1; g->o_g1 = q.o_g1; g->o_b1 = q.o_b1; g->o_ws = q.o_ws; g->o_g2 = q.o_g2;
-    g->o_b2 = q.o_b2; g->o_w2 = q.o_w2; g->o_W3 = q.o_W3; g->o_g3 = q.o_g3; g->o_b3 = q.o_b3;
-    g->o_Wfc = q.o_Wfc; g->o_bfc = q.o_bfc;
-    g->CP = rup(g->C, 32); g->KC = g->CP / 32;
-    g->F2P = g->F2 <= 16 ? 16 : g->F2 <= 32 ? 32 : 64;
-    g->NOT = g->F2P / 16;
-    g->F2K = std::max(32, g->F2P); g->KCW = g->F2K / 32;
-    g->TX = rup(g->T, 128);
-    g->NT = (g->T + 15) / 16; g->NBLK = (g->NT + 15) / 16;
-    g->LPs = g->P + 1;
-    g->KSF = (g->K1 + 16 + 31) / 32;
-    // s rows: FIR windows read up to element 256*NBLK + 32*KSF - 16; row stride = 4 mod 8 dwords so the
-    // 16 rows of one spatial-tile store land on distinct bank quads
-    g->SXs = 256 * g->NBLK + 32 * g->KSF - 8;
-    g->T1 = g->T / 4; g->T2 = g->T1 / 8; g->NF = g->F2 * g->T2;
-    const int nq = (g->T1 + 3) / 4;
-    g->RA = 4 * nq + 16;
-    g->NT1 = (8 * g->T2 + 15) / 16;
-    g->TZ = rup(std::max(4 * nq, 16 * g->NT1), 128);
-    if (g->T % 8 == 0) {
-        const int units = g->CP * g->TX / 8;
-        int u = (units + NTI - 1) / NTI, p = 1;
-        while (p < u) p *= 2;
-        g->PFU = p;
-    } else {
-        g->PFU = 0;
-    }
-    if (g->PFU > 16) return fail(EEGNET_EINVAL, "bf16 eval: C*T too large for one trial in registers");
-    const int r1 = std::max(g->CP * g->TX * 2, rup(g->F2P * g->RA * 4, 16) + g->F2K * g->TZ * 2);
-    g->offZ = rup(g->F2P * g->RA * 4, 16);
-    g->offS = rup(r1, 16);
-    g->offW1 = rup(g->offS + g->F2P * g->SXs * 2, 16);
-    g->offW2 = rup(g->offW1 + g->F1 * g->K1 * 4, 16);
-    g->offCo = rup(g->offW2 + g->F2P * K2 * 4, 16);
-    g->offL = rup(g->offCo + 4 * g->F2P * 4, 16);
-    g->lds = g->offL + NWI * NCLS * 4;
-    // classifier weights staged in LDS when they fit (cfg5: 16 KB), else read from global
-    const int offF = rup(g->lds, 16);
-    if (offF + NCLS * g->NF * 4 <= LDS_MAX) {
-        g->offF = offF;
-        g->lds = offF + NCLS * g->NF * 4;
-    }
+    if (int r = check_dims(d)) return r;
+    *g = geo_shape_bf16(model_dims(*d));
+    g->B = d->B;
+    g->eps = d->bn_eps;
     g->dbg = g_bf16_dbg;
+    if (g->PFU > 16) return fail(EEGNET_EINVAL, "bf16 eval: C*T too large for one trial in registers");
     if (g->lds > LDS_MAX)
         return fail(EEGNET_EINVAL, "bf16 eval: dims need %d B of LDS (> %d): C=%d T=%d F2=%d", g->lds, LDS_MAX,
                     g->C, g->T, g->F2);
     return 0;
-}
-
-// every shape-derived field equal (B, eps and the debug pointer are runtime in every instantiation)
-static bool same_geo_bf16(GeoI a, GeoI b) {
-    a.B = b.B = 0;
-    a.eps = b.eps = 0.f;
-    a.dbg = b.dbg = nullptr;
-    return memcmp(&a, &b, sizeof(GeoI)) == 0;
 }
 
 // The train step of the F2 > 16 path with 64 temporal taps (k_wpass_a<64> / k_wpass_e<64>) is refused:
@@ -664,22 +514,12 @@ int eegnet_param_count(const eegnet_dims* dims, int64_t* out) {
 
 int eegnet_x_pitch(const eegnet_dims* dims) {
     if (!dims) return fail(EEGNET_EINVAL, "dims is NULL");
-    return x_pitch_shape(*dims) && (dims->T & 3) ? (dims->T + 3) & ~3 : dims->T;
+    return x_pitch_shape(model_dims(*dims)) ? (dims->T + 3) & ~3 : dims->T;
 }
 
 int eegnet_wide_spec(const eegnet_dims* dims) {
-    Geo g;
-    memset(&g, 0, sizeof(g));
-    if (int r = make_geo(dims, &g, false)) return r;
-    if (!g.wide || g.K1 != 32) return 0;
-    if (same_shape_w5(g)) return 1;
-    std::string msg = "geometry differs from EEG_SHAPE_W5:";
-    char b[96];
-#define EEG_DIFF_(f, v) if (g.f != v) { snprintf(b, sizeof(b), " %s = %d (compiled %d)", #f, (int)g.f, v); msg += b; }
-    EEG_SHAPE_W5(EEG_DIFF_)
-#undef EEG_DIFF_
-    g_err = msg;
-    return 0;
+    if (int r = check_dims(dims)) return r;
+    return is_cfg5(model_dims(*dims));
 }
 
 int eegnet_workspace_bytes(const eegnet_dims* dims, size_t* out) {
@@ -802,7 +642,7 @@ int eegnet_forward_eval_bf16(const eegnet_dims* dims, const float* params, const
     ensure_attrs();
     hipStream_t s = (hipStream_t)stream;
     // cfg5: the time-chunked kernel, two workgroups per CU (eegnet_infer_bf16c.hip)
-    if (same_geo_bf16(g, kGeoCfg5))
+    if (is_cfg5(model_dims(g)))
         return launch(KID_INFER_BF16, "k_infer_bf16(cfg5)", k_infer_bf16_cfg5, dim3(std::min(g.B, 2 * device_cus())),
                       dim3(c5::NT), c5::LDS, s, g, params, bn_buffers, x, logits);
     // the whole-trial kernel, by the prefetch registers per thread

@@ -120,21 +120,9 @@ __device__ __forceinline__ void xi_stage_elems(const GeoI& g, const uint16_t* __
     }
 }
 
-// Compile-time geometry of BASELINE cfg5 (EEGNet-16,4 on 64ch x 512): the values make_geo_bf16
-// computes for those dims.  The host launches k_infer_bf16_cfg5 (eegnet_infer_bf16c.hip) only when its
-// runtime geometry equals this one field for field (B, eps and dbg excepted), so every loop bound,
-// stride and LDS offset folds to a constant there.
-constexpr GeoI kGeoCfg5 = {
-    0, 64, 512, 16, 4, 64, 32, 15,          // B, C, T, F1, D, F2, K1, P
-    64, 2, 64, 4, 64, 2, 512,               // CP, KC, F2P, NOT, F2K, KCW, TX
-    32, 2, 16, 2, 568,                      // NT, NBLK, LPs, KSF, SXs
-    128, 16, 1024, 144, 128, 8, 8,          // T1, T2, NF, RA, TZ, NT1, PFU
-    1e-5f,                                  // eps (runtime)
-    0, 512, 528, 544, 4640, 4704, 4768, 5792, 9888, 9952, 10016, 14112,   // o_w1 .. o_bfc
-    36864, 65536, 138240, 140288, 144384, 145408, 161920,                 // offZ .. offL, lds
-    145536,                                 // offF
-    nullptr};
-
+// The whole-trial kernel, for every geometry but BASELINE cfg5 (EEGNet-16,4 on 64ch x 512), which runs the
+// time-chunked k_infer_bf16_cfg5 (eegnet_infer_bf16c.hip); GeoI's shape fields come from geo_shape_bf16
+// (eegnet_geometry.h), whose value for the cfg5 dims, kGeoCfg5, that kernel's constants are checked against.
 template <int PFU>
 __global__ __launch_bounds__(NTI) void k_infer_bf16(GeoI g, const float* __restrict__ prm,
                                                     const float* __restrict__ bn,

@@ -668,7 +668,7 @@ __global__ __launch_bounds__(NT) void k_wpass_b2(Geo gin, const float* __restric
     float* W2s = Q + F2P * RB;
     float* W3s = W2s + F2P * K2;
     // cfg5: each wave's W3 fragments (row tile mp.jt, all 16 k-steps) live in 16 registers instead of
-    // an LDS table, so two workgroups fit per CU (make_geo_wide: ldsWB2 without the table, gridW2)
+    // an LDS table, so two workgroups fit per CU (geo_shape_wide: ldsWB2 without the table; make_geo: gridW2)
     constexpr bool W3R = SPEC && NT == 512;
     float* ws_ = W3R ? W3s : W3s + F2P * (F2P + 1);
     const int tid = threadIdx.x, lane = tid & 63;

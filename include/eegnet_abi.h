@@ -439,8 +439,8 @@ int eegnet_x_pitch(const eegnet_dims* dims);
 int eegnet_launch_grids(const eegnet_dims* dims, int fold_launch, int out[6]);
 
 /* 1 when `dims` run the wide kernels compiled for the EEGNet-16,4 64 x 512 geometry (compile-time
- * bounds and offsets), 0 when they run the generic wide / narrow kernels (for a wide K1 = 32 shape the
- * differing geometry fields are then in eegnet_last_error()), < 0 on invalid dims.  No GPU needed. */
+ * bounds and offsets), 0 when they run the generic wide / narrow kernels, < 0 on invalid dims.  No GPU
+ * needed. */
 int eegnet_wide_spec(const eegnet_dims* dims);
 
 /* sizeof(eegnet_dims), sizeof(eegnet_fold) and sizeof(eegnet_eval_fold) as this library was compiled: a

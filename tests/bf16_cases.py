@@ -167,7 +167,7 @@ class Case:
         return f"{self.C}x{self.T}-F{self.F1}D{self.D}-K{self.K1}"
 
 
-# PFU (make_geo_bf16, eegnet_host.hip): 0 when T % 8 != 0, else units = rup(C, 32) * rup(T, 128) / 8
+# PFU (geo_shape_bf16, eegnet_geometry.h): 0 when T % 8 != 0, else units = rup(C, 32) * rup(T, 128) / 8
 # 16-byte units over 512 threads, rounded up to a power of two.  Re-derived on paper for every row:
 #   64x512: 64*512/8 = 4096 -> 8          64x768: 64*768/8 = 6144 -> 12 -> 16 (units 12..15 of a thread lie
 #   32x1000: 32*1024/8 = 4096 -> 8        past row CP = 64 for most threads: the c < CP guard of xi_store)

@@ -108,10 +108,11 @@ def test_flag_and_kernel_id_constants_match_header():
 
 
 def test_cfg5_runs_the_compile_time_geometry_kernels():
-    """The wide kernels compiled for EEGNet-16,4 at 64 x 512 (EEG_SHAPE_W5) are launched only when the
-    run-time geometry equals the compiled one field for field; a layout change (coefficient block,
-    workspace, LDS carve-up) that is not mirrored there would silently fall back to the generic
-    kernels (cfg5 train 1.8M -> 1.4M trials/s).  No GPU needed."""
+    """The wide kernels compiled for EEGNet-16,4 at 64 x 512 are launched for exactly those dims, whatever
+    the batch; their compile-time geometry (kGeoW5, eegnet_geometry.h) is the host's own shape function
+    evaluated for them, so a layout change (coefficient block, workspace, LDS carve-up) reaches both at
+    once.  Any other shape runs the generic kernels (cfg5 train 1.4M instead of 1.8M trials/s).  No GPU
+    needed."""
     import ctypes
     from eegnetreplication_amd import _lib
     lib = _lib.load()

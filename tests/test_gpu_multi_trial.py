@@ -3,7 +3,7 @@ large enough that every workgroup of every pass runs its trial loop more than on
 
 The streaming passes split a batch over min(B, 2 CUs) workgroups, passes C / D and the eval forward
 over min(B, CUs), the F2 > 16 streaming passes over about CUs / ceil(F2 / 16) trial ranges
-(eegnet_host.hip make_geo / make_geo_wide).  Every other test of a shape that is not one of the
+(eegnet_host.hip make_geo).  Every other test of a shape that is not one of the
 compile-time ones (22 x 256 / 257 EEGNet-8,2, EEGNet-16,4 at 64 x 512) has B <= 40, so there each
 `for (b = b0; b < b1; ++b)` runs once: the register-staged prefetch of the next trial's x (k_pass_a,
 k_pass_e, k_infer, k_wpass_a / _e, k_winfer), of its v / d2 / r planes (k_pass_b, k_pass_dr, k_wpass_b,
