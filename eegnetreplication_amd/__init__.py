@@ -3,8 +3,10 @@
 Public surface mirrors ``eegnet_repl.model``: ``EEGNet``, ``train``, ``evaluate_model``; ``saliency``
 and ``relevance_maps`` give the eval-mode input gradients the reference gets from plain autograd;
 ``sliding_logits``, ``cropped_predict`` and ``evaluate_cropped`` classify every window of a continuous
-recording in place; ``exponential_moving_standardize`` and ``StreamStandardizer`` standardise a raw recording
-for them on the device, as the reference's preprocessing does.
+recording in place and ``epoch_logits`` the windows a cue table places (``epoch_starts``); ``design_bandpass``,
+``bandpass_filter`` / ``StreamBandpass`` and ``exponential_moving_standardize`` / ``StreamStandardizer``
+(together: ``preprocess_recording``) band-pass and standardise a raw recording for them on the device, as the
+reference's preprocessing does.
 The compute runs in ``libeegnet_hip.so`` (hand-written gfx950 HIP kernels, C-ABI in
 ``include/eegnet_abi.h``).
 """
@@ -13,8 +15,11 @@ from .model import EEGNet, FusedTrainer, evaluate_model, relevance_maps, salienc
 from .model import cropped_predict, evaluate_cropped, sliding_logits, window_starts  # noqa: F401
 from .folds import FoldBatch, FrozenFoldBatch, evaluate_folds  # noqa: F401
 from .ops import Shape  # noqa: F401
+from .model import epoch_logits, epoch_starts  # noqa: F401
 from .preprocess import StreamStandardizer, exponential_moving_standardize  # noqa: F401
+from .preprocess import StreamBandpass, bandpass_filter, design_bandpass, preprocess_recording  # noqa: F401
 
-__all__ = ["EEGNet", "FoldBatch", "FrozenFoldBatch", "FusedTrainer", "Shape", "StreamStandardizer", "cropped_predict",
-           "evaluate_cropped", "evaluate_folds", "evaluate_model", "exponential_moving_standardize", "relevance_maps",
-           "saliency", "sliding_logits", "train", "window_starts"]
+__all__ = ["EEGNet", "FoldBatch", "FrozenFoldBatch", "FusedTrainer", "Shape", "StreamBandpass", "StreamStandardizer",
+           "bandpass_filter", "cropped_predict", "design_bandpass", "epoch_logits", "epoch_starts", "evaluate_cropped",
+           "evaluate_folds", "evaluate_model", "exponential_moving_standardize", "preprocess_recording",
+           "relevance_maps", "saliency", "sliding_logits", "train", "window_starts"]

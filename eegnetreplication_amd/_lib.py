@@ -101,6 +101,13 @@ _SIGS = {
     "eegnet_forward_eval_windows": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int64,
                                                    ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp,
                                                    _vp]),
+    "eegnet_forward_eval_windows_at": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int64,
+                                                      ctypes.c_int64, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp,
+                                                      _vp]),
+    "eegnet_fir_max_taps": (ctypes.c_int, []),
+    "eegnet_fir_chunk": (ctypes.c_int, []),
+    "eegnet_fir": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,
+                                  ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),
     "eegnet_ems_chunk": (ctypes.c_int, []),
     "eegnet_ems_scratch_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
     "eegnet_ems": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,

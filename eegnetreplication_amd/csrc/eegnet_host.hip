@@ -243,6 +243,7 @@ static void set_attrs_shape() {
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_eval_folds<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_infer_win<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipFuncSetAttribute((const void*)k_infer_win<K1, CC, TT, FF, WinAtCall>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 template <class... S>
@@ -985,6 +986,27 @@ static int ems_launch(const EmsCall& ec, const void* x, float* y, double* state,
     return launch(KID_NONE, "k_ems_out", k_ems_out<T>, grid, dim3(EMS_NT), 0, s, ec, (const T*)x, carry, y);
 }
 
+constexpr int64_t FIR_MAX_GRID = 2147483647;          // hipLaunchKernel's grid.x
+
+// the two launches of eegnet_fir on rows of T: the outputs (when there are any), then the next history
+template <class T>
+static int fir_launch(const FirCall& fc, const void* x, const double* taps, const double* hist_in, double* hist_out,
+                      float* y, hipStream_t s) {
+    if (fc.n_out > 0)
+        if (int r = launch(KID_NONE, "k_fir", k_fir<T>, dim3((unsigned)(fc.n_rows * fc.n_chunks)), dim3(FIR_NT),
+                           (size_t)fir_lds_doubles(fc.L) * sizeof(double), s, fc, (const T*)x, taps, hist_in, y)) return r;
+    const long long nh = fc.n_rows * (long long)(fc.L - 1);
+    if (!hist_out || nh == 0) return 0;
+    return launch(KID_NONE, "k_fir_hist", k_fir_hist<T>, dim3((unsigned)((nh + FIR_NT - 1) / FIR_NT)), dim3(FIR_NT), 0, s,
+                  fc, (const T*)x, hist_in, hist_out);
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+static bool bytes_overlap(const void* a, double na, const void* b, double nb) {
+    const double a0 = (double)(uintptr_t)a, b0 = (double)(uintptr_t)b;
+    return a && b && na > 0 && nb > 0 && a0 < b0 + nb && b0 < a0 + na;
+}
+
 extern "C" {
 
 int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
@@ -1120,6 +1142,131 @@ int eegnet_forward_eval_windows(const eegnet_dims* dims, const float* params, co
     if (!probs && !pred) return 0;
     return launch(KID_NONE, "k_win_reduce", k_win_reduce, dim3((unsigned)n_rec), dim3(NTWR), 0, s, logits, wc.W, probs,
                   pred);
+}
+
+int eegnet_forward_eval_windows_at(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                                   const float* rec, int64_t n_rec, int64_t n_samples, int64_t pitch,
+                                   const int64_t* starts, const int32_t* rec_index, int64_t n_windows, float* logits,
+                                   void* stream) {
+    if (!dims) return fail(EEGNET_EINVAL, "dims is NULL");
+    eegnet_dims d = *dims;
+    d.B = 1;                                          // dims->B is ignored: the table sizes the call
+    Geo g;
+    if (int r = make_geo_narrow(&d, &g, "windows at a table")) return r;
+    if (g.XP != g.T) return fail(EEGNET_EINVAL, "windows at a table: x_pitch must be 0 or T (the rows' pitch is `pitch`)");
+    if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
+    if (int r = check_ptrs(rec, "rec", logits, "logits")) return r;
+    if (int r = check_ptrs(starts, "starts")) return r;
+    if (n_rec < 1 || n_rec > 2147483647)
+        return fail(EEGNET_EINVAL, "windows at a table: n_rec must be in [1, 2^31) (got %lld)", (long long)n_rec);
+    if (n_samples < g.T)
+        return fail(EEGNET_EINVAL, "windows at a table: n_samples = %lld is shorter than one window (T = %d)",
+                    (long long)n_samples, g.T);
+    if (pitch < n_samples)
+        return fail(EEGNET_EINVAL, "windows at a table: pitch = %lld is below n_samples = %lld", (long long)pitch,
+                    (long long)n_samples);
+    if (((uintptr_t)rec & 3) || ((uintptr_t)starts & 7) || ((uintptr_t)rec_index & 3))
+        return fail(EEGNET_EINVAL, "windows at a table: rec, starts and rec_index must be aligned to their element size");
+    if (n_windows < 1 || n_windows > 2147483647)
+        return fail(EEGNET_EINVAL, "windows at a table: n_windows must be in [1, 2^31) (got %lld)", (long long)n_windows);
+    d.B = (int)n_windows;                             // every window is one trial of the eval forward
+    if (make_geo(&d, &g)) {
+        const std::string why = g_err;
+        return fail(EEGNET_EINVAL, "windows at a table: %d windows exceed the batch the eval forward takes (%s)", d.B,
+                    why.c_str());
+    }
+    WinAtCall ac;
+    ac.rec = rec;
+    ac.pitch = pitch;
+    ac.hop = 0;
+    ac.W = 0;
+    ac.total = d.B;
+    ac.vec = 0;
+    ac.starts = (const long long*)starts;
+    ac.rec_index = rec_index;
+    ac.last = n_samples - g.T;
+    ac.n_rec = (int)n_rec;
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_shape(g, [&](auto sh) {
+        return launch(KID_NONE, "k_infer_win(at)", k_infer_win<SHAPE_OF(sh), WinAtCall>, dim3(g.grid), dim3(NTH),
+                      g.ldsI * 4, s, g, params, bn_buffers, ac, logits);
+    });
+}
+
+int eegnet_fir_max_taps(void) { return FIR_MAX_TAPS; }
+
+int eegnet_fir_chunk(void) { return FIR_CH; }
+
+int eegnet_fir(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, int64_t x_pitch, const double* taps,
+               int n_taps, float* y, int64_t y_pitch, const double* hist_in, double* hist_out, int mode, void* stream) {
+    if (mode < EEGNET_FIR_WHOLE || mode > EEGNET_FIR_TAIL)
+        return fail(EEGNET_EINVAL, "eegnet_fir: unknown mode %d", mode);
+    if (mode != EEGNET_FIR_TAIL)
+        if (int r = check_ptrs(x, "x")) return r;
+    if (int r = check_ptrs(y, "y", taps, "taps")) return r;
+    if (n_taps < 1 || n_taps > FIR_MAX_TAPS)
+        return fail(EEGNET_EINVAL, "eegnet_fir: n_taps must be in [1, %d] (got %d)", FIR_MAX_TAPS, n_taps);
+    if (mode != EEGNET_FIR_NEXT && (n_taps & 1) == 0)
+        return fail(EEGNET_EINVAL, "eegnet_fir: a zero-phase filter needs an odd n_taps (got %d); only a continuation "
+                    "call takes an even one", n_taps);
+    const int L = n_taps, M = (L - 1) / 2;
+    if (n_rows < 1) return fail(EEGNET_EINVAL, "eegnet_fir: n_rows must be >= 1 (got %lld)", (long long)n_rows);
+    const int64_t n_min = mode == EEGNET_FIR_FIRST ? L : 1;
+    if (mode == EEGNET_FIR_TAIL) {
+        if (n_samples != 0)
+            return fail(EEGNET_EINVAL, "eegnet_fir: the tail call takes no samples (n_samples = %lld)", (long long)n_samples);
+    } else if (n_samples < n_min) {
+        return fail(EEGNET_EINVAL, "eegnet_fir: n_samples must be >= %lld%s (got %lld)", (long long)n_min,
+                    mode == EEGNET_FIR_FIRST ? " = n_taps for a stream's first block" : "", (long long)n_samples);
+    }
+    const bool need_in = (mode == EEGNET_FIR_NEXT || mode == EEGNET_FIR_TAIL) && L > 1;
+    const bool need_out = (mode == EEGNET_FIR_FIRST || mode == EEGNET_FIR_NEXT) && L > 1;
+    if (need_in && !hist_in) return fail(EEGNET_EINVAL, "eegnet_fir: this mode reads the history: hist_in is NULL");
+    if (need_out && !hist_out) return fail(EEGNET_EINVAL, "eegnet_fir: this mode writes the history: hist_out is NULL");
+    FirCall fc;
+    fc.n_rows = n_rows;
+    fc.n = n_samples;
+    fc.L = L;
+    fc.M = M;
+    fc.head_reflect = mode == EEGNET_FIR_WHOLE || mode == EEGNET_FIR_FIRST;
+    fc.tail_reflect = mode == EEGNET_FIR_WHOLE || mode == EEGNET_FIR_TAIL;
+    fc.t_lo = fc.head_reflect ? 0 : -M;
+    fc.n_out = mode == EEGNET_FIR_WHOLE ? n_samples : mode == EEGNET_FIR_FIRST ? n_samples - M
+               : mode == EEGNET_FIR_NEXT ? n_samples : M;
+    // a stream's recording holds at least n_taps samples (its first block does): both ends reflect M
+    fc.refl = mode == EEGNET_FIR_WHOLE ? std::min<int64_t>(M, n_samples - 1) : M;
+    fc.n_chunks = fc.n_out > 0 ? (fc.n_out - 1) / FIR_CH + 1 : 0;
+    if (fc.n_chunks > FIR_MAX_GRID / n_rows || (int64_t)(L - 1) > FIR_MAX_GRID / n_rows * FIR_NT)
+        return fail(EEGNET_EINVAL, "eegnet_fir: n_rows = %lld rows of %lld chunks (%d outputs each) exceed the grid limit "
+                    "of %lld workgroups", (long long)n_rows, (long long)fc.n_chunks, FIR_CH, (long long)FIR_MAX_GRID);
+    if (mode != EEGNET_FIR_TAIL && x_pitch < n_samples)
+        return fail(EEGNET_EINVAL, "eegnet_fir: x_pitch = %lld is below n_samples = %lld", (long long)x_pitch,
+                    (long long)n_samples);
+    if (y_pitch < fc.n_out)
+        return fail(EEGNET_EINVAL, "eegnet_fir: y_pitch = %lld is below the %lld outputs of a row", (long long)y_pitch,
+                    (long long)fc.n_out);
+    fc.x_pitch = x_pitch;
+    fc.y_pitch = y_pitch;
+    const uintptr_t xa = x_is_f64 ? 7 : 3;
+    if (((uintptr_t)x & xa) || ((uintptr_t)y & 3) || ((uintptr_t)taps & 7) || ((uintptr_t)hist_in & 7) ||
+        ((uintptr_t)hist_out & 7))
+        return fail(EEGNET_EINVAL, "eegnet_fir: x, y, taps and the histories must be aligned to their element size");
+    // a workgroup's outputs would overwrite inputs its neighbours still read: no in-place filtering.  The
+    // extents are the rows' bounding ranges, first byte of the first row to last byte of the last.
+    const double xb = ((double)(n_rows - 1) * (double)x_pitch + (double)n_samples) * (x_is_f64 ? 8.0 : 4.0);
+    const double yb = ((double)(n_rows - 1) * (double)y_pitch + (double)fc.n_out) * 4.0;
+    const double hb = (double)n_rows * (double)(L - 1) * 8.0;
+    if (mode != EEGNET_FIR_TAIL && bytes_overlap(x, xb, y, yb))
+        return fail(EEGNET_EINVAL, "eegnet_fir: y overlaps x (filtering in place is not supported)");
+    if (need_in && need_out && bytes_overlap(hist_in, hb, hist_out, hb))
+        return fail(EEGNET_EINVAL, "eegnet_fir: hist_out overlaps hist_in (the call reads one and writes the other)");
+    if (!need_in) hist_in = nullptr;
+    if (!need_out) hist_out = nullptr;
+    if (fc.n_out == 0 && !hist_out) return 0;          // (the tail of a one-tap filter)
+    hipStream_t s = (hipStream_t)stream;
+    return x_is_f64 ? fir_launch<double>(fc, x, taps, hist_in, hist_out, y, s)
+                    : fir_launch<float>(fc, x, taps, hist_in, hist_out, y, s);
 }
 
 // chunks per row and workgroups of an eegnet_ems call; the sizes are checked before anything is multiplied

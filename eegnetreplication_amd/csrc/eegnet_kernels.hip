@@ -47,5 +47,6 @@
 #include "eegnet_infer_bf16.hip"
 #include "eegnet_infer_bf16c.hip"
 #include "eegnet_ems.hip"
+#include "eegnet_fir.hip"
 #include "eegnet_geometry.h"
 #include "eegnet_host.hip"

@@ -10,6 +10,10 @@
 // so logits[r, w] carries the bits eegnet_forward_eval gives for the copy.  infer_trial itself is not
 // called: it fetches the next trial through x_prefetch, and it stays as it is (eegnet_trial.hip's header).
 //
+// eegnet_forward_eval_windows_at runs the same kernel with the window origin read from a table (cue
+// epoching in place): k_infer_win's second variant, on a WinAtCall, takes window p from sample starts[p] of
+// recording rec_index[p], both clamped into the recordings, and picks the load width per window.
+//
 // Overlapping windows share nothing: the 'same' padding makes a window's first and last FIR outputs its
 // own, the pool4 phase follows hop mod 4, and a shared block 1 would not be bit-equal to k_infer.
 
@@ -28,6 +32,35 @@ struct WinCall {
 __device__ __forceinline__ const float* win_row0(const WinCall& wc, int C, int p) {
     const int r = p / wc.W, w = p - r * wc.W;
     return wc.rec + (long long)r * C * wc.pitch + (long long)w * wc.hop;
+}
+
+// The windows of a table: window p is samples [starts[p], starts[p] + T) of recording rec_index[p]
+// (nullable: recording 0).  `total` is the table's length; hop, W and vec are unused.
+struct WinAtCall : WinCall {
+    const long long* starts;      // [total], device
+    const int* rec_index;         // [total], device, nullable
+    long long last;               // n_samples - T: the largest start
+    int n_rec;
+};
+
+// where window p starts and whether its rows take 16-byte loads (both wave-uniform)
+struct WinOrg {
+    const float* row0;
+    int vec;
+};
+
+__device__ __forceinline__ WinOrg win_org(const WinCall& wc, int C, int, int p) { return {win_row0(wc, C, p), wc.vec}; }
+
+// A start is clamped into [0, last] and a recording index into [0, n_rec): whatever the table holds, every
+// load lies inside the recordings.
+__device__ __forceinline__ WinOrg win_org(const WinAtCall& ac, int C, int T, int p) {
+    long long st = ac.starts[p];
+    st = st < 0 ? 0 : st > ac.last ? ac.last : st;
+    int r = ac.rec_index ? ac.rec_index[p] : 0;
+    r = r < 0 ? 0 : r >= ac.n_rec ? ac.n_rec - 1 : r;
+    const float* row0 = ac.rec + (long long)r * C * ac.pitch + st;
+    const int vec = (T & 3) == 0 && (ac.pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(row0) & 15) == 0;
+    return {row0, vec};
 }
 
 // x_prefetch of a window: element i of the flattened [C][T] window is sample i % T of row i / T.  The
@@ -73,9 +106,9 @@ __device__ __forceinline__ void win_prefetch(const float* __restrict__ xb, long 
 // One 1024-thread workgroup per window in flight, windows strided over a flat grid (k_infer's for
 // B = n_rec W).  The next window's load is issued at the top of a trial and stored over the x rows
 // behind their last reader, the spatial GEMM.
-template <int K1, int CC, int TT, int FF>
+template <int K1, int CC, int TT, int FF, class Call = WinCall>
 __global__ __launch_bounds__(NTH) void k_infer_win(Geo g, const float* __restrict__ prm,
-                                                   const float* __restrict__ bn, WinCall wc,
+                                                   const float* __restrict__ bn, Call wc,
                                                    float* __restrict__ logits) {
     EEG_DIMS(g);
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -94,7 +127,10 @@ __global__ __launch_bounds__(NTH) void k_infer_win(Geo g, const float* __restric
     const int o = wave;
     const bool row_on = o < F2;
     float pf[PF];
-    if ((int)blockIdx.x < wc.total) win_prefetch<PF>(win_row0(wc, C, blockIdx.x), wc.pitch, wc.vec, C, T, pf, tid);
+    if ((int)blockIdx.x < wc.total) {
+        const WinOrg org = win_org(wc, C, T, blockIdx.x);
+        win_prefetch<PF>(org.row0, wc.pitch, org.vec, C, T, pf, tid);
+    }
     __syncthreads();
     x_store<PF>(pf, C, T, RS, LP, Xs, tid);
     __syncthreads();
@@ -103,7 +139,10 @@ __global__ __launch_bounds__(NTH) void k_infer_win(Geo g, const float* __restric
     for (int b = blockIdx.x; b < wc.total; b += gridDim.x) {
         const int bnx = b + gridDim.x;
         const bool nxt = bnx < wc.total;
-        if (nxt) win_prefetch<PF>(win_row0(wc, C, bnx), wc.pitch, wc.vec, C, T, pf, tid);
+        if (nxt) {
+            const WinOrg org = win_org(wc, C, T, bnx);
+            win_prefetch<PF>(org.row0, wc.pitch, org.vec, C, T, pf, tid);
+        }
         spatial_mfma<KS>(Xs, w.aw, Ss, C, F2, NT16, RS, LP, wave, lane);
         __syncthreads();                                   // s rows complete; the x rows are free
         if (row_on)

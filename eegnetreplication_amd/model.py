@@ -530,6 +530,68 @@ def cropped_predict(model, rec, hop):
     return probs, pred, logits
 
 
+def epoch_starts(onsets, sfreq=128.0, tmin=0.5):
+    """Start sample of the epoch of every cue: ``onsets + round(tmin * sfreq)``, an int64 tensor.  With the
+    defaults and T = 257 these are the reference's epochs, ``mne.Epochs(tmin=0.5, tmax=2.5)`` at 128 Hz: 257
+    samples starting 64 samples after the cue."""
+    onsets = torch.as_tensor(onsets)
+    if onsets.is_floating_point() or onsets.dtype == torch.bool:
+        raise ValueError(f"cue onsets are sample indices: expected integers (got {onsets.dtype})")
+    return onsets.to(torch.int64) + int(round(float(tmin) * float(sfreq)))
+
+
+def _host_table(t, what, dtype, lo, hi, why):
+    """A host table (list, numpy array, CPU tensor) as a CPU tensor of ``dtype``, every entry in [lo, hi]."""
+    t = torch.as_tensor(t)
+    if t.numel() == 0 and t.dim() == 1:
+        t = t.to(torch.int64)                                   # (an empty list comes as float32)
+    if t.is_floating_point() or t.dtype == torch.bool or t.dim() != 1:
+        raise ValueError(f"{what} must be a 1-D table of integers (got {t.dtype} {list(t.shape)})")
+    t = t.to(torch.int64)
+    if t.numel() and (int(t.min()) < lo or int(t.max()) > hi):
+        bad = int(((t < lo) | (t > hi)).nonzero()[0])
+        raise ValueError(f"{what}[{bad}] = {int(t[bad])} is outside [{lo}, {hi}] ({why})")
+    return t.to(dtype).contiguous()
+
+
+def epoch_logits(model, rec, starts, rec_index=None):
+    """Logits [W, 4] of the T-sample windows a table places in continuous recordings -- cue epoching in
+    place: window w is samples [starts[w], starts[w] + T) of recording ``rec_index[w]`` of ``rec`` [R, C, N]
+    (recording 0 when ``rec_index`` is None, and for a 2-D ``rec`` [C, N]), read where it lies, and row w is
+    bit-identical to ``model.eval()`` on that window copied out (``epoch_starts`` gives the reference's
+    starts from the cue onsets).  A table given on the host -- a list, a numpy array or a CPU tensor -- is
+    checked there (ValueError for a start outside [0, N - T] or a recording outside [0, R)) and uploaded; a
+    device table (``starts`` int64, ``rec_index`` int32) is used as it lies and never read by the host, so
+    the call can be captured in a graph -- the kernel then clamps an out-of-range entry into the recordings
+    instead of reading outside them.  Always eval semantics, whatever ``model.training`` is, and that mode
+    is left untouched.  F1*D > 16 models raise NotImplementedError."""
+    if rec.dim() not in (2, 3) or rec.shape[-2] != model.C or rec.shape[-1] < model.T:
+        raise RuntimeError(f"expected a recording [{model.C}, N] or [R, {model.C}, N] with N >= {model.T}, "
+                           f"got {list(rec.shape)}")
+    R, N = (1 if rec.dim() == 2 else int(rec.shape[0])), int(rec.shape[-1])
+    # host tables first: their check needs no device
+    if not (isinstance(starts, torch.Tensor) and starts.device.type == "cuda"):
+        starts = _host_table(starts, "starts", torch.int64, 0, N - model.T,
+                             f"a window of T = {model.T} samples in a recording of {N}")
+    if rec_index is not None and not (isinstance(rec_index, torch.Tensor) and rec_index.device.type == "cuda"):
+        rec_index = _host_table(rec_index, "rec_index", torch.int32, 0, R - 1, f"{R} recordings")
+        if rec_index.numel() != starts.numel():
+            raise ValueError(f"rec_index holds {rec_index.numel()} entries, starts {starts.numel()}")
+    require_device(rec, "EEGNet recording")
+    if rec.dtype != torch.float32:
+        raise RuntimeError(f"epoch_logits expects a float32 recording (got {rec.dtype})")
+    starts = starts.to(rec.device)
+    rec_index = None if rec_index is None else rec_index.to(rec.device)
+    flat = model.flat_parameters()
+    require_device(flat, "EEGNet parameters")
+    with torch.no_grad():
+        try:
+            return ops.forward_eval_windows_at(model.shape, flat, model.flat_bn_buffers(), rec.detach(), starts,
+                                               rec_index)
+        except RuntimeError as e:
+            _not_supported(e)
+
+
 def evaluate_cropped(model, loader, hop) -> float:
     """Accuracy in percent of the crop-averaged prediction (``cropped_predict``) over a loader of
     ``([b, C, N], labels)`` batches of long trials: ``evaluate_model`` for cropped evaluation, with the

@@ -276,6 +276,113 @@ def ems(x, out=None, *, factor_new=1e-3, init_block=1000, eps=1e-10, state=None,
     return out
 
 
+FIR_WHOLE, FIR_FIRST, FIR_NEXT, FIR_TAIL = 0, 1, 2, 3     # include/eegnet_abi.h EEGNET_FIR_*
+
+
+def fir_chunk() -> int:
+    """eegnet_fir_chunk: the outputs of one workgroup of the FIR kernel.  Host-side only."""
+    return int(_lib.load().eegnet_fir_chunk())
+
+
+def fir_max_taps() -> int:
+    """eegnet_fir_max_taps: the longest filter eegnet_fir takes.  Host-side only."""
+    return int(_lib.load().eegnet_fir_max_taps())
+
+
+def fir(x, taps, out=None, *, mode=FIR_WHOLE, hist_in=None, hist_out=None, lead=None):
+    """FIR filtering of continuous recordings (eegnet_fir): per row y[t] = sum_k taps[k] u[t + M - k],
+    M = (L - 1) // 2, in float64 on the device, rounded to float32 once.  ``x`` is [R, C, N] float32 or float64
+    on the device and is read in place when its rows lie at one pitch (a contiguous tensor or a time slice of
+    one); anything else is made contiguous first.  ``taps``: a contiguous float64 [L] device tensor.
+    ``mode``: FIR_WHOLE, the zero-phase call with both ends reflected (N outputs); FIR_FIRST, a stream's
+    first block (N >= L, N - M outputs, ``hist_out`` written); FIR_NEXT, a continuation (``hist_in`` read,
+    ``hist_out`` written, N outputs); FIR_TAIL, the stream's last M outputs from ``hist_in`` (``x`` is None
+    and ``lead`` = (R, C)).  The histories are contiguous float64 [R * C, L - 1] device tensors, two different
+    ones.  ``out``: a float32 [R, C, outputs] device tensor whose rows lie at one pitch and that does not
+    overlap ``x`` (ValueError), else a new contiguous one."""
+    require_device(taps, "taps")
+    if taps.dtype != torch.float64 or taps.dim() != 1 or not taps.is_contiguous():
+        raise ValueError("taps must be a contiguous float64 [L] tensor on the device")
+    L = int(taps.shape[0])
+    M = (L - 1) // 2
+    if mode == FIR_TAIL:
+        if x is not None or lead is None:
+            raise ValueError("the tail call takes no samples: x is None and lead = (R, C)")
+        R, C = (int(v) for v in lead)
+        N, xp, is64, dev = 0, 0, False, taps.device
+    else:
+        require_device(x, "x")
+        if x.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError(f"fir expects float32 or float64 input (got {x.dtype})")
+        if x.dim() != 3:
+            raise RuntimeError(f"expected recordings [R, C, N], got {list(x.shape)}")
+        R, C, N = x.shape
+        xp = _row_pitch(x)
+        if xp is None:
+            x, xp = x.contiguous(), N
+        is64, dev = x.dtype == torch.float64, x.device
+    n_out = {FIR_WHOLE: N, FIR_FIRST: max(N - M, 0), FIR_NEXT: N, FIR_TAIL: M}[mode]
+    if out is None:
+        out = torch.empty((R, C, n_out), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (R, C, n_out) or out.dtype != torch.float32 or out.device != dev or _row_pitch(out) is None:
+        raise ValueError(f"out must be a float32 {[R, C, n_out]} tensor on {dev} whose rows lie at one pitch "
+                         f"(last stride 1)")
+    for name, h in (("hist_in", hist_in), ("hist_out", hist_out)):
+        if h is not None and (h.dtype != torch.float64 or tuple(h.shape) != (R * C, L - 1) or not h.is_contiguous()
+                              or h.device != dev):
+            raise ValueError(f"{name} must be a contiguous float64 [{R * C}, {L - 1}] tensor on {dev}")
+    if R * C == 0 or (N == 0 and mode != FIR_TAIL):
+        return out
+    op = _row_pitch(out)
+    if mode != FIR_TAIL and n_out > 0:
+        # the library rejects it too (EEGNET_EINVAL): said here as the ValueError the Python surface promises
+        x0, x1 = x.data_ptr(), x.data_ptr() + ((R * C - 1) * xp + N) * x.element_size()
+        y0, y1 = out.data_ptr(), out.data_ptr() + ((R * C - 1) * op + n_out) * 4
+        if x0 < y1 and y0 < x1:
+            raise ValueError("out overlaps x: filtering in place is not supported (a workgroup's outputs would "
+                             "overwrite inputs its neighbours still read)")
+    _lib.check(_lib.load().eegnet_fir(
+        _ptr(x), ctypes.c_int(is64), ctypes.c_int64(R * C), ctypes.c_int64(N), ctypes.c_int64(xp), _ptr(taps),
+        ctypes.c_int(L), _ptr(out), ctypes.c_int64(op), _ptr(hist_in), _ptr(hist_out), ctypes.c_int(mode), _stream()),
+        "eegnet_fir")
+    return out
+
+
+def forward_eval_windows_at(shape: Shape, flat_params, bn_flat, rec, starts, rec_index=None):
+    """Eval-mode forward of the T-sample windows a table places (eegnet_forward_eval_windows_at): window w is
+    samples [starts[w], starts[w] + T) of recording rec_index[w] (None: recording 0).  ``rec`` as
+    ``forward_eval_windows`` takes it; ``starts`` int64 [W] and ``rec_index`` int32 [W] are contiguous device
+    tensors the host never reads -- the kernel clamps an entry into the recordings.  Returns logits [W, 4],
+    each row bit-identical to ``forward_eval`` on that window."""
+    require_device(rec, "rec")
+    if rec.dtype != torch.float32:
+        raise RuntimeError(f"forward_eval_windows_at expects float32 input (got {rec.dtype})")
+    if rec.dim() not in (2, 3) or rec.shape[-2] != shape.C:
+        raise RuntimeError(f"expected a recording [{shape.C}, N] or [R, {shape.C}, N], got {list(rec.shape)}")
+    r3 = rec.unsqueeze(0) if rec.dim() == 2 else rec
+    R, C, N = r3.shape
+    pitch = _row_pitch(r3)
+    if pitch is None:
+        r3, pitch = r3.contiguous(), N
+    for name, t, dt in (("starts", starts, torch.int64), ("rec_index", rec_index, torch.int32)):
+        if t is None and name == "rec_index":
+            continue
+        require_device(t, name)
+        if t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != rec.device:
+            raise ValueError(f"{name} must be a contiguous {dt} [W] tensor on {rec.device}")
+    W = int(starts.shape[0])
+    if rec_index is not None and int(rec_index.shape[0]) != W:
+        raise ValueError(f"rec_index holds {int(rec_index.shape[0])} entries, starts {W}")
+    logits = torch.empty((W, NCLS), dtype=torch.float32, device=rec.device)
+    if W == 0:
+        return logits
+    _lib.check(_lib.load().eegnet_forward_eval_windows_at(
+        ctypes.byref(shape.dims(1)), _ptr(flat_params), _ptr(bn_flat), _ptr(r3), ctypes.c_int64(R), ctypes.c_int64(N),
+        ctypes.c_int64(pitch), _ptr(starts), _ptr(rec_index), ctypes.c_int64(W), _ptr(logits), _stream()),
+        "eegnet_forward_eval_windows_at")
+    return logits
+
+
 SEED_DLOGITS, SEED_LOGIT, SEED_CE = 0, 1, 2     # include/eegnet_abi.h EEGNET_SEED_*
 _SEED_KINDS = {"dlogits": SEED_DLOGITS, "logit": SEED_LOGIT, "ce": SEED_CE}
 

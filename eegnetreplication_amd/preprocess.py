@@ -1,24 +1,29 @@
-"""Preprocessing of continuous recordings on the device: exponential moving standardisation, the step the
-reference applies to every recording before it cuts trials out of it (``raw_exponential_moving_standardize``,
-dataset.py:45-70).  ``raw recording -> exponential_moving_standardize -> sliding_logits`` runs without a host
-step; ``StreamStandardizer`` is the same call fed block by block with the state carried along.
+"""Preprocessing of continuous recordings on the device: the zero-phase FIR band-pass and the exponential moving
+standardisation the reference applies to every recording before it cuts trials out of it (``raw.filter(4., 38.,
+fir_design='firwin')``, dataset.py:113-125; ``raw_exponential_moving_standardize``, dataset.py:45-70).
+``raw recording -> bandpass_filter -> exponential_moving_standardize -> epoch_logits / sliding_logits`` runs
+without a host step; ``StreamBandpass`` and ``StreamStandardizer`` are the same calls fed block by block with
+the state carried along.  Resampling is not here: the recording is at its final rate.
 """
 
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
 from . import ops
 from .ops import require_device
 
 
-def _as_rows(rec, what):
+def _as_rows(rec, what, step="exponential moving standardisation"):
     """``rec`` [C, N] or [R, C, N] on the device, float32 or float64 -> ([R, C, N] view, was 2-D)."""
     if rec.dim() not in (2, 3):
         raise RuntimeError(f"expected a recording [C, N] or [R, C, N], got {list(rec.shape)}")
     require_device(rec, what)
     if rec.dtype not in (torch.float32, torch.float64):
-        raise RuntimeError(f"exponential moving standardisation expects a float32 or float64 recording "
+        raise RuntimeError(f"{step} expects a float32 or float64 recording "
                            f"(got {rec.dtype})")
     return (rec.unsqueeze(0), True) if rec.dim() == 2 else (rec, False)
 
@@ -97,3 +102,176 @@ class StreamStandardizer:
         if block.shape[-1] > 0:
             self.state = state
         return y
+
+
+# ----------------------------------------------------------------------------------------------
+# zero-phase FIR band-pass (dataset.py:113-125: raw.filter(4., 38., fir_design='firwin'))
+# ----------------------------------------------------------------------------------------------
+_HAMMING_LENGTH_FACTOR = 3.3          # taps = factor * sfreq / transition width, for a Hamming window
+
+
+def _odd(n):
+    return n + 1 - n % 2
+
+
+def _lowpass(numtaps, cutoff, sfreq):
+    """A Hamming-windowed-sinc low-pass of ``numtaps`` (odd) taps with its -6 dB point at ``cutoff`` Hz, scaled to
+    unit gain at DC: ``scipy.signal.firwin(numtaps, cutoff, window='hamming', fs=sfreq)`` in plain numpy."""
+    c = cutoff / (0.5 * sfreq)
+    m = np.arange(numtaps) - 0.5 * (numtaps - 1)
+    h = c * np.sinc(c * m)
+    if numtaps > 1:
+        h = h * (0.54 + 0.46 * np.cos(np.linspace(-np.pi, np.pi, numtaps)))
+    h = 0.5 * (h + h[::-1])               # the window's two halves differ in the last bit: exactly linear phase
+    return h / math.fsum(h)               # (the exactly rounded sum: the DC gain is 1 to the last bit or two)
+
+
+def design_bandpass(sfreq=128.0, l_freq=4.0, h_freq=38.0):
+    """Taps (float64 numpy, odd length, symmetric) of the zero-phase band-pass that ``mne`` designs for
+    ``raw.filter(l_freq, h_freq, fir_design='firwin')`` with its defaults, by the rule ``mne`` documents:
+
+      * transition bands  l_trans = min(max(0.25 l_freq, 2), l_freq),
+                          h_trans = min(max(0.25 h_freq, 2), sfreq / 2 - h_freq);
+      * length            ceil(3.3 sfreq / min(l_trans, h_trans)), made odd (3.3: the Hamming window);
+      * taps              a Hamming-windowed-sinc low-pass with its -6 dB point at h_freq + h_trans / 2, of
+                          round(3.3 sfreq / h_trans) taps made odd, centred in the full length, minus the
+                          low-pass at l_freq - l_trans / 2 of round(3.3 sfreq / l_trans) taps made odd; each
+                          low-pass has unit gain at DC, so the band-pass has none.
+
+    At 128 Hz, 4-38 Hz: 213 taps (transitions 2 and 9.5 Hz); at 250 Hz: 413.  Pure numpy: scipy is not needed
+    at run time.  ``mne`` itself is not installed where this package is developed, so the agreement with
+    ``mne.filter.create_filter`` is by construction from its documented rule and is not checked by a test; taps
+    that ``mne`` computed (``create_filter(...)``) can be passed to ``bandpass_filter`` unchanged."""
+    sfreq, l_freq, h_freq = float(sfreq), float(l_freq), float(h_freq)
+    if not 0.0 < l_freq < h_freq < 0.5 * sfreq:
+        raise ValueError(f"expected 0 < l_freq < h_freq < sfreq / 2 (got {l_freq}, {h_freq}, sfreq {sfreq})")
+    l_trans = min(max(0.25 * l_freq, 2.0), l_freq)
+    h_trans = min(max(0.25 * h_freq, 2.0), 0.5 * sfreq - h_freq)
+    n = _odd(int(math.ceil(_HAMMING_LENGTH_FACTOR * sfreq / min(l_trans, h_trans))))
+    h = np.zeros(n)
+    for sign, cutoff, trans in ((1.0, h_freq + 0.5 * h_trans, h_trans), (-1.0, l_freq - 0.5 * l_trans, l_trans)):
+        k = _odd(int(round(_HAMMING_LENGTH_FACTOR * sfreq / trans)))
+        off = (n - k) // 2
+        h[off:n - off] += sign * _lowpass(k, cutoff, sfreq)
+    return h
+
+
+def _device_taps(taps, device):
+    """float64 taps on ``device``: a float64 device tensor is used as it lies, anything else is uploaded."""
+    if isinstance(taps, torch.Tensor) and taps.device.type == "cuda":
+        if taps.dtype != torch.float64 or taps.dim() != 1:
+            raise ValueError(f"device taps must be a float64 [L] tensor (got {taps.dtype} {list(taps.shape)})")
+        return taps.contiguous()
+    t = np.ascontiguousarray(taps.detach().numpy() if isinstance(taps, torch.Tensor) else taps, dtype=np.float64)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError(f"taps must be a non-empty 1-D array (got shape {list(t.shape)})")
+    return torch.from_numpy(t).to(device)
+
+
+def bandpass_filter(rec, taps, out=None):
+    """Zero-phase FIR filtering of continuous recordings, per channel row:
+
+        y[t] = sum_k taps[k] u[t + M - k],   M = (L - 1) / 2,
+
+    u being the row extended past its ends as ``mne``'s 'reflect_limited' padding extends it
+    (u[-j] = 2 x[0] - x[j], u[N-1+j] = 2 x[N-1] - x[N-1-j] for j up to min(M, N - 1), zero beyond): what
+    ``raw.filter`` computes with symmetric taps.  ``rec`` is [C, N] or [R, C, N], float32 or float64, on the
+    device, read in place when its last stride is 1 and its rows lie at one pitch.  ``taps``: an odd number of
+    them (``design_bandpass()``, or ``mne``'s own) as a float64 device tensor, used as it lies -- what a graph
+    capture must pass -- or a numpy array / CPU tensor, uploaded once per call.  Returns float32 of the same
+    shape; all arithmetic is float64 on the device, the result is rounded once, and the same inputs give the
+    same bits.  ``out``: a float32 tensor of that shape to receive the result; it must not overlap ``rec``
+    (ValueError): there is no in-place filtering."""
+    if out is not None and out.shape != rec.shape:
+        raise ValueError(f"out must have the recording's shape {list(rec.shape)} (got {list(out.shape)})")
+    r3, squeeze = _as_rows(rec, "EEGNet recording", "the band-pass filter")
+    o3 = None
+    if out is not None:
+        require_device(out, "out")
+        o3 = out.unsqueeze(0) if squeeze else out
+    t = _device_taps(taps, rec.device)
+    if t.shape[0] % 2 == 0:
+        raise ValueError(f"a zero-phase filter needs an odd number of taps (got {int(t.shape[0])})")
+    with torch.no_grad():
+        y = ops.fir(r3.detach(), t, o3)
+    if out is not None:
+        return out
+    return y[0] if squeeze else y
+
+
+def preprocess_recording(rec, taps, factor_new=1e-3, init_block_size=1000, eps=1e-10):
+    """The reference's per-recording preprocessing after resampling: ``bandpass_filter(rec, taps)``, then
+    ``exponential_moving_standardize`` of the result in place.  A composition of the two calls, nothing fused;
+    float32 of the recording's shape, ready for ``epoch_logits`` / ``sliding_logits``."""
+    y = bandpass_filter(rec, taps)
+    return exponential_moving_standardize(y, factor_new, init_block_size, eps, out=y)
+
+
+class StreamBandpass:
+    """``bandpass_filter`` fed block by block: the filter of a pseudo-online decoder, the companion of
+    ``StreamStandardizer``.
+
+    ``n_rows_or_shape``: the number of channel rows C, or the leading shape of every block -- ``(C,)`` for
+    blocks [C, n], ``(R, C)`` for blocks [R, C, n].  ``taps``: as ``bandpass_filter`` takes them (L of them, L
+    odd, M = (L - 1) / 2), uploaded at the first push.
+
+    A zero-phase filter looks M samples ahead, so the output lags the input by M samples: the first
+    ``push(block)`` must hold at least L samples (ValueError otherwise -- the head reflection is then the
+    block's own) and returns n - M samples; every later push takes any n >= 1 and returns n samples;
+    ``flush()`` returns the last M samples, reflected about the recording's end, and ends the stream
+    (``reset()`` starts another).  Everything returned, concatenated, equals ``bandpass_filter`` of the
+    whole recording bit for bit.  The last L - 1 input samples per row are carried as float64 in two device
+    buffers that alternate (a call reads one and writes the other)."""
+
+    def __init__(self, n_rows_or_shape, taps):
+        lead = (int(n_rows_or_shape),) if isinstance(n_rows_or_shape, int) else tuple(int(s) for s in n_rows_or_shape)
+        if len(lead) not in (1, 2) or min(lead) < 1:
+            raise ValueError(f"expected a row count or a leading shape (C,) or (R, C), got {n_rows_or_shape!r}")
+        n_taps = int(taps.shape[0]) if hasattr(taps, "shape") and len(taps.shape) == 1 else len(taps)
+        if n_taps < 1 or n_taps % 2 == 0:
+            raise ValueError(f"a zero-phase filter needs an odd number of taps (got {n_taps})")
+        self.lead, self.taps, self.n_taps = lead, taps, n_taps
+        self._hist = None                  # [current, spare] once the first block is in
+        self._done = False
+
+    def reset(self):
+        self._hist, self._done = None, False
+
+    def _lead3(self):
+        return (1, self.lead[0]) if len(self.lead) == 1 else self.lead
+
+    def push(self, block):
+        if tuple(block.shape[:-1]) != self.lead:
+            raise RuntimeError(f"expected a block {list(self.lead)} + [n], got {list(block.shape)}")
+        if self._done:
+            raise RuntimeError("the stream was flushed: reset() starts another")
+        n, L = int(block.shape[-1]), self.n_taps
+        first = self._hist is None
+        if first and n < L:
+            raise ValueError(f"the first block must hold at least the filter's {L} samples (got {n}): the head "
+                             f"reflection has to be the block's own")
+        if not first and n < 1:
+            raise ValueError("a block must hold at least one sample")
+        b3, squeeze = _as_rows(block, "EEGNet recording block", "the band-pass filter")
+        R, C = self._lead3()
+        if first:
+            self.taps = _device_taps(self.taps, block.device)
+            hist = [torch.empty((R * C, L - 1), dtype=torch.float64, device=block.device) for _ in range(2)]
+            cur, new = None, hist[0]
+        else:
+            hist = self._hist
+            cur, new = hist
+        with torch.no_grad():
+            y = ops.fir(b3.detach(), self.taps, mode=ops.FIR_FIRST if first else ops.FIR_NEXT, hist_in=cur, hist_out=new)
+        self._hist = [hist[0], hist[1]] if first else [new, cur]
+        return y[0] if squeeze else y
+
+    def flush(self):
+        if self._hist is None:
+            raise RuntimeError("flush() before the first push")
+        if self._done:
+            raise RuntimeError("the stream was flushed: reset() starts another")
+        self._done = True
+        with torch.no_grad():
+            y = ops.fir(None, self.taps, mode=ops.FIR_TAIL, hist_in=self._hist[0], lead=self._lead3())
+        return y[0] if len(self.lead) == 1 else y

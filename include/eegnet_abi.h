@@ -11,6 +11,8 @@
  *   that fine-tuning loop for many models at once (per-subject fine-tuning, k folds each) -> eegnet_frozen_step_folds
  *   the per-epoch validation loop src/eegnet_repl/model.py:151-172, many folds at once -> eegnet_eval_folds
  *   raw_exponential_moving_standardize  src/eegnet_repl/dataset.py:45-70 -> eegnet_ems
+ *   raw.filter(4., 38., fir_design='firwin')  src/eegnet_repl/dataset.py:113-125 -> eegnet_fir
+ *   mne.Epochs(tmin=0.5, tmax=2.5) + model.eval()  src/eegnet_repl/dataset.py:223-224 -> eegnet_forward_eval_windows_at
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer (hipMalloc / torch CUDA tensor) unless noted.  The library never
@@ -355,6 +357,60 @@ int eegnet_window_count(const eegnet_dims* dims, int64_t n_samples, int64_t hop,
 int eegnet_forward_eval_windows(const eegnet_dims* dims, const float* params, const float* bn_buffers,
                                 const float* rec, int64_t n_rec, int64_t n_samples, int64_t pitch,
                                 int64_t hop, float* logits, float* probs, int32_t* pred, void* stream);
+
+/* Cue epoching in place: the eval forward of n_windows windows whose origins come from a table instead of
+ * w*hop.  `rec`, n_rec, n_samples and pitch are eegnet_forward_eval_windows's.  starts, int64 [n_windows], and
+ * rec_index, int32 [n_windows] (nullable: every window is of recording 0), are DEVICE arrays the host never
+ * reads: window w is samples [starts[w], starts[w] + T) of recording rec_index[w], and logits[w] (fp32
+ * [n_windows, 4]) is bit-identical to eegnet_forward_eval on that window copied out as one [1, C, T] trial.
+ * The kernel clamps a start into [0, n_samples - T] and a recording index into [0, n_rec): no table makes it
+ * read outside the recordings (an out-of-range entry gives the logits of the clamped window; callers that
+ * want an error check the table on the host, as the Python side does for host tables).  The load width is
+ * chosen per window on the device; the bits do not depend on it.  dims->B is ignored; x_pitch must be 0 or T;
+ * n_rec >= 1, n_samples >= T, 1 <= n_windows, and n_windows must be a batch eegnet_forward_eval takes;
+ * F1*D <= 16 only.  One launch, no atomics, no allocation, no host synchronisation: capturable in a hipGraph.
+ * The validation needs no GPU. */
+int eegnet_forward_eval_windows_at(const eegnet_dims* dims, const float* params, const float* bn_buffers,
+                                   const float* rec, int64_t n_rec, int64_t n_samples, int64_t pitch,
+                                   const int64_t* starts, const int32_t* rec_index, int64_t n_windows,
+                                   float* logits, void* stream);
+
+/* FIR filtering of continuous recordings: the reference's zero-phase band-pass (raw.filter(4., 38.,
+ * fir_design='firwin'), dataset.py:113-125; a 213-tap FIR at 128 Hz) for any taps, the step in front of
+ * eegnet_ems.  Per row, with taps h[0..L-1] (fp64, on the device; L = n_taps) and M = (L-1)/2,
+ *     y[t] = sum_{k=0..L-1} h[k] u[t + M - k]
+ * with u the row extended past the recording's ends as mne's 'reflect_limited' padding extends it:
+ * u[-j] = 2 x[0] - x[j] and u[N-1+j] = 2 x[N-1] - x[N-1-j] for 1 <= j <= min(M, N-1), zero beyond.  All
+ * arithmetic is fp64 -- one fused multiply-add per tap in the order k = 0..L-1 from a zero start -- and y is
+ * rounded to fp32 once.  An output's value is a function of the taps and of its L values of u alone: not of
+ * the chunking, of n_rows, of a pitch or an alignment, nor of the mode that produced it.
+ *   EEGNET_FIR_WHOLE  the zero-phase call on whole rows: n_samples >= 1 in, n_samples out; both ends reflect.
+ *   EEGNET_FIR_FIRST  a stream's first block: n_samples >= L in, the n_samples - M outputs whose right
+ *                     support is present out (outputs 0 .. n_samples-M-1 of the recording); the left end
+ *                     reflects; hist_out receives the block's last L-1 samples as fp64 [n_rows][L-1].
+ *   EEGNET_FIR_NEXT   a continuation: n_samples >= 1 in, n_samples out, lagging the input by M samples (the
+ *                     first output is the one M samples before the block's first sample); the left context is
+ *                     hist_in, and hist_out receives the last L-1 samples of history + block.  A block shorter
+ *                     than L-1 leaves a history that is part old history, part block; hist_out must not be
+ *                     hist_in (the caller ping-pongs two buffers).  Takes an even L as well.
+ *   EEGNET_FIR_TAIL   the stream's end: n_samples = 0 (x is not read and may be NULL), the last M outputs of
+ *                     the recording out, the right end reflected about the last sample of hist_in.
+ * The outputs of FIRST, NEXT.. and TAIL laid end to end are the WHOLE call's on the concatenated blocks, bit
+ * for bit.  x holds n_rows rows of n_samples valid elements, fp32 or fp64 (x_is_f64), row i at x + i*x_pitch
+ * elements, any 4- / 8-byte alignment (a time slice of a larger buffer is passed as it lies); y is fp32, row i
+ * at y + i*y_pitch; x_pitch >= n_samples, y_pitch >= the outputs of a row.  No byte outside a row's valid
+ * samples is read and none outside its outputs is written.  Filtering in place is not supported: a call whose
+ * y rows' bounding byte range meets the x rows' is rejected.  1 <= n_taps <= eegnet_fir_max_taps() (2049);
+ * WHOLE, FIRST and TAIL need an odd n_taps.  One workgroup per row and chunk of eegnet_fir_chunk() outputs
+ * (both compile-time constants, host only); n_rows * chunks <= 2^31 - 1.  One launch for the outputs and one
+ * for the history, on `stream`; no atomics, no allocation, no host synchronisation: capturable in a hipGraph.
+ * The validation needs no GPU. */
+enum { EEGNET_FIR_WHOLE = 0, EEGNET_FIR_FIRST = 1, EEGNET_FIR_NEXT = 2, EEGNET_FIR_TAIL = 3 };
+int eegnet_fir_max_taps(void);
+int eegnet_fir_chunk(void);
+int eegnet_fir(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, int64_t x_pitch,
+               const double* taps, int n_taps, float* y, int64_t y_pitch, const double* hist_in,
+               double* hist_out, int mode, void* stream);
 
 /* Exponential moving standardisation of continuous recordings: the reference's
  * raw_exponential_moving_standardize (dataset.py:45-70), the step in front of eegnet_forward_eval_windows.
