@@ -235,8 +235,25 @@ struct FinArgs {
 // ticket blocks of the five passes in a workspace
 enum { TK_A = 0, TK_B, TK_C, TK_D, TK_E, TK_COUNT };
 
-// Fold-indexed launches (eegnet_train_step_folds): blockIdx.y is the fold; a fold's pointers come
-// from its eegnet_fold entry and its workspace regions sit at the same offsets in every workspace.
+// What each pass's finalize takes, and where its partial-row length and LDS floats sit in Geo: the one table
+// behind the host's FinArgs (pass_fin, eegnet_host.hip), k_fin's launch, eegnet_stage_sums and the fold
+// launches' fold_fin.  ce: single-model calls run the CE only in PC_CE mode.
+struct PassInfo {
+    bool bn, nbt, grads, loss, ce, adam;
+    int update_running, Geo::*ncols, Geo::*lds;
+};
+constexpr PassInfo kPass[TK_COUNT] = {
+    //         bn     nbt    grads  loss   ce     adam   update_running
+    /* A */ {true,  false, false, false, false, false, 1, &Geo::nA, &Geo::ldsA},
+    /* B */ {true,  true,  false, false, false, false, 1, &Geo::nB, &Geo::ldsB},
+    /* C */ {false, false, true,  true,  true,  false, 0, &Geo::nC, &Geo::ldsC},
+    /* D */ {false, false, true,  false, false, false, 0, &Geo::nD, &Geo::ldsD},
+    /* E */ {false, false, true,  false, false, true,  0, &Geo::nE, &Geo::ldsE},
+};
+
+// Byte offsets of a workspace's regions (make_layout, eegnet_host.hip): the host adds them to the call's
+// workspace, a fold-indexed launch (eegnet_train_step_folds: blockIdx.y is the fold, its pointers come from
+// its eegnet_fold entry) to each fold's -- the regions sit at the same offsets in every workspace.
 struct WsOff {
     unsigned long long cnt, partA, partB, partC, partD, partE, sums, stats, coef, d2, E1, E2, dp2, dl, s, v, q3, r3;
 };
@@ -303,25 +320,27 @@ __device__ __forceinline__ long long fold_row(const int64_t* __restrict__ perm, 
     return perm ? perm[row0 + bb] : row0 + bb;
 }
 
-__device__ __forceinline__ FinArgs fold_fin(const FoldCall& fc, const eegnet_fold& f, int tk, int update_running,
-                                            int ce, bool nbt, bool adam, int nparam) {
+// pass TK's finalize arguments of a fold: the flags kPass gives the pass, the pointers from the fold's record
+template <int TK>
+__device__ __forceinline__ FinArgs fold_fin(const FoldCall& fc, const eegnet_fold& f, int nparam) {
+    constexpr PassInfo p = kPass[TK];
     char* ws = (char*)f.ws;
     FinArgs a;
     a.part2 = (double*)(ws + fc.off.sums);
-    a.cnt = tkw((unsigned*)(ws + fc.off.cnt), tk * NCNT);
+    a.cnt = tkw((unsigned*)(ws + fc.off.cnt), TK * NCNT);
     a.stats = (double*)(ws + fc.off.stats);
     a.coef = (float*)(ws + fc.off.coef);
     a.bn = f.bn_buffers;
     a.grads = f.grads;
     a.loss = f.losses ? f.losses + fc.slot : nullptr;
-    a.nbt = nbt ? f.num_batches_tracked : nullptr;
-    a.update_running = update_running;
-    a.ce = ce;
-    a.tpass = tk;
-    a.params = adam ? f.params : nullptr;
-    a.adam_m = adam ? f.adam_state : nullptr;
-    a.adam_v = adam ? f.adam_state + nparam : nullptr;
-    a.step = adam ? f.step : nullptr;
+    a.nbt = p.nbt ? f.num_batches_tracked : nullptr;
+    a.update_running = p.update_running;
+    a.ce = p.ce;
+    a.tpass = TK;
+    a.params = p.adam ? f.params : nullptr;
+    a.adam_m = p.adam ? f.adam_state : nullptr;
+    a.adam_v = p.adam ? f.adam_state + nparam : nullptr;
+    a.step = p.adam ? f.step : nullptr;
     a.lr = fc.lr; a.b1 = fc.b1; a.b2 = fc.b2; a.eps = fc.eps;
     return a;
 }

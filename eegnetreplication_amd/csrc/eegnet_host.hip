@@ -21,11 +21,6 @@ static inline size_t rupz(size_t a, size_t m) { return (a + m - 1) / m * m; }
 
 constexpr size_t CNT_BYTES = (size_t)TK_COUNT * NCNT * TKS * 4;     // a multiple of 16
 
-struct WsLayout {
-    size_t cnt, partA, partB, partC, partD, partE, sums, stats, coef, d2, E1, E2, dp2, dl, s, v, q3, r3;
-    size_t total;
-};
-
 static int device_cus() {
     static int cus = 0;
     if (cus == 0) {
@@ -121,8 +116,8 @@ static int make_geo(const eegnet_dims* d, Geo* g, bool launch = true) {
     return launch ? check_launch(*g) : 0;
 }
 
-static WsLayout make_layout(const Geo& g) {
-    WsLayout L;
+// the regions of a geometry's workspace (WsOff, eegnet_common.h); returns its size in bytes
+static size_t make_layout(const Geo& g, WsOff& L) {
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = rupz(o + bytes, 256); return r; };
     // ticket words first: zero when the workspace is allocated (ops.new_workspace), re-armed by each pass's
@@ -147,8 +142,7 @@ static WsLayout make_layout(const Geo& g) {
     // C (r) and D (q, r) instead of recomputing them from d2
     L.q3 = take(per);
     L.r3 = take(per);
-    L.total = o;
-    return L;
+    return o;
 }
 
 static uint64_t mix_key(uint64_t seed, uint64_t offset) {
@@ -294,33 +288,55 @@ static int dispatch_shape(const Geo& g, F&& f) {
     return g.K1 == 32 ? f(Shape<32, 0, 0, 0>{}) : f(Shape<64, 0, 0, 0>{});
 }
 
-// the finalize arguments of one pass (ticket words `tk`); Adam is attached to pass E by attach_adam
-static FinArgs fin_args(const WsLayout& L, char* ws, int tk, float* bn, float* grads, float* loss,
-                        int update_running, int ce, int64_t* nbt = nullptr) {
-    FinArgs f;
-    memset(&f, 0, sizeof(f));
-    f.part2 = (double*)(ws + L.sums);
-    f.cnt = tkw((unsigned*)(ws + L.cnt), tk * NCNT);
-    f.stats = (double*)(ws + L.stats);
-    f.coef = (float*)(ws + L.coef);
-    f.bn = bn; f.grads = grads; f.loss = loss;
-    f.update_running = update_running; f.ce = ce;
-    f.nbt = nbt;
-    f.tpass = tk;
-    return f;
-}
+// One call of the five-pass step, as its launches see it.  An entry point fills what it has; the rest
+// stays null / off.  A fold-indexed launch (fc.folds, nf folds in the grid's y) has no workspace or
+// pointers of its own: its kernels take every pointer and their FinArgs from the fold's record, so they
+// are launched with null pointers and a zeroed FinArgs.
+struct StepCall {
+    char* ws;                             // the workspace (null in fold launches) and its layout
+    WsOff off;
+    hipStream_t s;
+    const float* params = nullptr;        // written only when pass E runs Adam
+    float* bn = nullptr;
+    const float* x = nullptr;
+    const uint8_t *m2 = nullptr, *m3 = nullptr;
+    const float* dlogits = nullptr;
+    const int64_t* labels = nullptr;
+    float *logits = nullptr, *grads = nullptr, *loss = nullptr;
+    int64_t* nbt = nullptr;
+    int c_mode = 0;                       // PassCMode of pass C; without PC_BWD it writes the logits alone
+    bool adam = false;                    // pass E's finalize runs Adam (else: gradients only)
+    float* adam_state = nullptr;          // exp_avg, then exp_avg_sq
+    int32_t* step = nullptr;
+    float lr = 0.f, b1 = 0.f, b2 = 0.f, eps = 0.f;
+    FoldCall fc = {};
+    int nf = 1, only = -1;                // only >= 0: that pass alone (eegnet_train_stage)
+    StepCall(const Geo& g, void* w, void* stream) : ws((char*)w), s((hipStream_t)stream) { make_layout(g, off); }
+    // a plane or the partial rows of the workspace, as the kernels' float pointer
+    float* at(unsigned long long o) const { return ws ? (float*)(ws + o) : nullptr; }
+};
 
-// the Adam fields of a call (adam_state: exp_avg, then exp_avg_sq), attached to pass E's finalize
-static FinArgs adam_args(float* adam_state, int nparam, int32_t* step, float lr, float b1, float b2, float eps) {
-    FinArgs a;
-    memset(&a, 0, sizeof(a));
-    a.adam_m = adam_state; a.adam_v = adam_state ? adam_state + nparam : nullptr; a.step = step;
-    a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps;
-    return a;
-}
-static void attach_adam(FinArgs* fe, float* params, const FinArgs& adam) {
-    fe->params = params; fe->adam_m = adam.adam_m; fe->adam_v = adam.adam_v; fe->step = adam.step;
-    fe->lr = adam.lr; fe->b1 = adam.b1; fe->b2 = adam.b2; fe->eps = adam.eps;
+static FinArgs no_fin() { FinArgs f; memset(&f, 0, sizeof(f)); return f; }
+
+// the finalize arguments of pass `tk`: what kPass (eegnet_common.h) gives the pass, from the call
+static FinArgs pass_fin(const Geo& g, const StepCall& c, int tk) {
+    FinArgs f = no_fin();
+    if (c.fc.folds) return f;             // (fold_fin, on the device)
+    const PassInfo& p = kPass[tk];
+    f.part2 = (double*)(c.ws + c.off.sums);
+    f.cnt = tkw((unsigned*)(c.ws + c.off.cnt), tk * NCNT);
+    f.stats = (double*)(c.ws + c.off.stats);
+    f.coef = c.at(c.off.coef);
+    f.bn = p.bn ? c.bn : nullptr; f.nbt = p.nbt ? c.nbt : nullptr;
+    f.grads = p.grads ? c.grads : nullptr; f.loss = p.loss ? c.loss : nullptr;
+    f.update_running = p.update_running; f.ce = p.ce && (c.c_mode & PC_CE);
+    f.tpass = tk;
+    if (p.adam && c.adam) {
+        f.params = const_cast<float*>(c.params);
+        f.adam_m = c.adam_state; f.adam_v = c.adam_state + g.nparam; f.step = c.step;
+        f.lr = c.lr; f.b1 = c.b1; f.b2 = c.b2; f.eps = c.eps;
+    }
+    return f;
 }
 
 // the dims the SPEC instantiations of the wide kernels are compiled for (kGeoW5, eegnet_geometry.h)
@@ -330,124 +346,123 @@ static bool spec_w5(const Geo& g) { return is_cfg5(model_dims(g)); }
 // so the grid does not touch the numerics)
 static int grid_wpass_b(const Geo& g, bool sp) { return sp ? std::min(2 * g.gridS, g.B * g.NOC) : g.gridS; }
 
-// a plane or the partial rows of a workspace, as the kernels' float pointer
-static float* at(char* ws, size_t off) { return (float*)(ws + off); }
-
 // F2 > 16: passes A, B (no reduction), B2 (BN3 statistics)
-static int run_forward_wide(const Geo& g, const WsLayout& L, char* ws, const float* params, float* bn,
-                            const float* x, const uint8_t* m2, int update_running, int64_t* nbt, hipStream_t s) {
-    const FinArgs fa = fin_args(L, ws, TK_A, bn, nullptr, nullptr, update_running, 0);
-    const FinArgs fb = fin_args(L, ws, TK_B, bn, nullptr, nullptr, update_running, 0, nbt);
+static int run_forward_wide(const Geo& g, const StepCall& c) {
+    const WsOff& L = c.off;
     const bool sp = spec_w5(g);       // the SPEC instantiations (cfg5 shape, compile-time geometry)
     return dispatch_shape(g, [&](auto sh) {
         constexpr int K1 = decltype(sh)::K1;
         if (int r = launch(KID_WA, "k_wpass_a", sp ? k_wpass_a<K1, K1 == 32> : k_wpass_a<K1>, dim3(g.gridS),
-                           dim3(NTW), g.ldsWA * 4, s, g, params, x, at(ws, L.s), at(ws, L.v), at(ws, L.partA), fa))
-            return r;
+                           dim3(NTW), g.ldsWA * 4, c.s, g, c.params, c.x, c.at(L.s), c.at(L.v), c.at(L.partA),
+                           pass_fin(g, c, TK_A))) return r;
         if (int r = launch(KID_WB, "k_wpass_b", sp ? k_wpass_b<K1, K1 == 32> : k_wpass_b<K1>,
-                           dim3(grid_wpass_b(g, sp)), dim3(NTW), g.ldsWB * 4, s, g, params, at(ws, L.coef),
-                           at(ws, L.v), m2, at(ws, L.d2), at(ws, L.E1), at(ws, L.E2))) return r;
+                           dim3(grid_wpass_b(g, sp)), dim3(NTW), g.ldsWB * 4, c.s, g, c.params, c.at(L.coef),
+                           c.at(L.v), c.m2, c.at(L.d2), c.at(L.E1), c.at(L.E2))) return r;
         return launch(KID_WB2, "k_wpass_b2", sp ? k_wpass_b2<NTB2, true> : k_wpass_b2<NTB2>, dim3(g.gridW2),
-                      dim3(NTB2), g.ldsWB2 * 4, s, g, params, at(ws, L.d2), at(ws, L.q3), at(ws, L.r3),
-                      at(ws, L.partB), fb);
+                      dim3(NTB2), g.ldsWB2 * 4, c.s, g, c.params, c.at(L.d2), c.at(L.q3), c.at(L.r3),
+                      c.at(L.partB), pass_fin(g, c, TK_B));
     });
 }
 
-static int run_backward_wide(const Geo& g, const WsLayout& L, char* ws, float* params, const float* x,
-                             const uint8_t* m2, const uint8_t* m3, const float* dlogits, const int64_t* labels,
-                             float* logits, float* grads, float* loss, int c_mode, const FinArgs* adam,
-                             hipStream_t s) {
-    const float* coef = (const float*)(ws + L.coef);
-    const float* dl = dlogits ? dlogits : (const float*)(ws + L.dl);
-    const FinArgs fc = fin_args(L, ws, TK_C, nullptr, grads, loss, 0, (c_mode & PC_CE) ? 1 : 0);
-    const FinArgs fd = fin_args(L, ws, TK_D, nullptr, grads, nullptr, 0, 0);
-    FinArgs fe = fin_args(L, ws, TK_E, nullptr, grads, nullptr, 0, 0);
-    if (adam) attach_adam(&fe, params, *adam);
+// the column-parallel reduction + finalize `fin` of a split wide pass (k_coltail, eegnet_finalize.hip)
+static int coltail(const Geo& g, const StepCall& c, const char* name, int fin, unsigned long long part, int nrows,
+                   int ncols, const FinArgs& fa, int scr) {
     const bool sp = spec_w5(g);
-    // the column-parallel reduction + finalize `fin` of a split pass (k_coltail, eegnet_finalize.hip)
-    auto coltail = [&](const char* name, int fin, size_t part, int nrows, int ncols, const FinArgs& fa, int scr) {
-        const int nb = (ncols + 63) / 64;
-        const size_t lds = 8 * (size_t)std::max(2 + (NTCT / 64) * 64, tail_s_doubles(ncols) + scr);
-        auto k = fin == 3 ? (sp ? k_coltail<3, true> : k_coltail<3>)
-               : fin == 4 ? (sp ? k_coltail<4, true> : k_coltail<4>) : (sp ? k_coltail<5, true> : k_coltail<5>);
-        return launch(KID_CTAIL, name, k, dim3(nb), dim3(NTCT), lds, s, g, params, at(ws, part), nrows, ncols, fa);
-    };
-    if (int r = launch(KID_WC, "k_wpass_c(bwd)", sp ? k_wpass_c<NTB2, true> : k_wpass_c<NTB2>, dim3(g.gridW2),
-                       dim3(NTB2), g.ldsWC * 4, s, g, params, coef, at(ws, L.r3), m3, dlogits, labels, logits,
-                       at(ws, L.dl), at(ws, L.partC), c_mode, fc)) return r;
-    if (g.splitC)
-        if (int r = coltail("k_coltail(C)", 3, L.partC, g.gridW2, g.nC, fc, 0)) return r;
+    const int nb = (ncols + 63) / 64;
+    const size_t lds = 8 * (size_t)std::max(2 + (NTCT / 64) * 64, tail_s_doubles(ncols) + scr);
+    auto k = fin == 3 ? (sp ? k_coltail<3, true> : k_coltail<3>)
+           : fin == 4 ? (sp ? k_coltail<4, true> : k_coltail<4>) : (sp ? k_coltail<5, true> : k_coltail<5>);
+    return launch(KID_CTAIL, name, k, dim3(nb), dim3(NTCT), lds, c.s, g, c.params, c.at(part), nrows, ncols, fa);
+}
+
+// Pass C, the one launch line of each path.  With PC_BWD it is the backward's first pass; without
+// (eegnet_forward_train) it writes the logits alone: no dl, no partial rows, no finalize.
+static int run_pass_c(const Geo& g, const StepCall& c) {
+    const WsOff& L = c.off;
+    const bool bwd = c.c_mode & PC_BWD;
+    const FinArgs fa = bwd ? pass_fin(g, c, TK_C) : no_fin();
+    float *const dl = bwd ? c.at(L.dl) : nullptr, *const part = bwd ? c.at(L.partC) : nullptr;
+    if (g.wide) {
+        const bool sp = spec_w5(g);
+        if (int r = launch(KID_WC, bwd ? "k_wpass_c(bwd)" : "k_wpass_c(fwd)", sp ? k_wpass_c<NTB2, true> : k_wpass_c<NTB2>,
+                           dim3(g.gridW2), dim3(NTB2), g.ldsWC * 4, c.s, g, c.params, c.at(L.coef), c.at(L.r3), c.m3,
+                           c.dlogits, c.labels, c.logits, dl, part, c.c_mode, fa)) return r;
+        return bwd && g.splitC ? coltail(g, c, "k_coltail(C)", 3, L.partC, g.gridW2, g.nC, fa, 0) : 0;
+    }
+    return dispatch_shape(g, [&](auto sh) {
+        return launch(KID_C, bwd ? "k_pass_c(bwd)" : "k_pass_c(fwd)",
+                      c.fc.folds ? k_pass_c<SHAPE_OF(sh), true> : k_pass_c<SHAPE_OF(sh)>, dim3(g.grid, c.nf),
+                      dim3(64 * g.nwC), g.ldsC * 4, c.s, g, c.params, c.at(L.coef), c.at(L.r3), c.m3, c.dlogits,
+                      c.labels, c.logits, dl, part, c.c_mode, fa, c.fc);
+    });
+}
+
+// F2 > 16: passes C, D, E, each with its k_coltail where its rows are wide
+static int run_backward_wide(const Geo& g, const StepCall& c) {
+    const WsOff& L = c.off;
+    const float* dl = c.dlogits ? c.dlogits : c.at(L.dl);
+    const FinArgs fd = pass_fin(g, c, TK_D), fe = pass_fin(g, c, TK_E);
+    const bool sp = spec_w5(g);
+    if (int r = run_pass_c(g, c)) return r;
     if (int r = launch(KID_WD, "k_wpass_d", sp ? k_wpass_d<NTB2, true> : k_wpass_d<NTB2>, dim3(g.grid),
-                       dim3(NTB2), g.ldsWD * 4, s, g, params, coef, at(ws, L.d2), at(ws, L.E1), at(ws, L.E2),
-                       at(ws, L.q3), at(ws, L.r3), m2, m3, dl, at(ws, L.dp2), at(ws, L.partD), fd)) return r;
+                       dim3(NTB2), g.ldsWD * 4, c.s, g, c.params, c.at(L.coef), c.at(L.d2), c.at(L.E1), c.at(L.E2),
+                       c.at(L.q3), c.at(L.r3), c.m2, c.m3, dl, c.at(L.dp2), c.at(L.partD), fd)) return r;
     if (g.splitD)
-        if (int r = coltail("k_coltail(D)", 4, L.partD, g.grid, g.nD, fd, 0)) return r;
+        if (int r = coltail(g, c, "k_coltail(D)", 4, L.partD, g.grid, g.nD, fd, 0)) return r;
     if (int r = dispatch_shape(g, [&](auto sh) {
             constexpr int K1 = decltype(sh)::K1;
             return launch(KID_WE, "k_wpass_e", sp ? k_wpass_e<K1, K1 == 32> : k_wpass_e<K1>, dim3(g.gridS), dim3(NTW),
-                          g.ldsWE * 4, s, g, params, coef, x, at(ws, L.s), at(ws, L.v), at(ws, L.dp2),
-                          at(ws, L.partE), fe);
+                          g.ldsWE * 4, c.s, g, c.params, c.at(L.coef), c.x, c.at(L.s), c.at(L.v), c.at(L.dp2),
+                          c.at(L.partE), fe);
         })) return r;
     // one partial row per trial range (k_wpass_e's chunk workgroups share it, disjoint columns)
     if (g.splitE)
-        return coltail("k_coltail(E)", 5, L.partE, g.gridS / g.NOC, g.nE, fe, fin5_scratch_doubles(g.K1, g.F1, g.o_g2));
+        return coltail(g, c, "k_coltail(E)", 5, L.partE, g.gridS / g.NOC, g.nE, fe,
+                       fin5_scratch_doubles(g.K1, g.F1, g.o_g2));
     return 0;
 }
 
-// fc.folds != nullptr: fold-indexed launch over nf folds (grid y); the other pointers are unused
-// only >= 0: that pass alone (eegnet_train_stage)
-static int run_forward(const Geo& g, const WsLayout& L, char* ws, const float* params, float* bn,
-                       const float* x, const uint8_t* m2, int update_running, int64_t* nbt, hipStream_t s,
-                       const FoldCall& fc = FoldCall{}, int nf = 1, int only = -1) {
-    if (g.wide) return run_forward_wide(g, L, ws, params, bn, x, m2, update_running, nbt, s);
-    const FinArgs fa = fin_args(L, ws, TK_A, bn, nullptr, nullptr, update_running, 0);
-    const FinArgs fb = fin_args(L, ws, TK_B, bn, nullptr, nullptr, update_running, 0, nbt);
+// passes A and B
+static int run_forward(const Geo& g, const StepCall& c) {
+    if (g.wide) return run_forward_wide(g, c);
+    const WsOff& L = c.off;
+    const bool fold = c.fc.folds;
     return dispatch_shape(g, [&](auto sh) {
-        if (only < 0 || only == 0)
-            if (int r = launch(KID_A, "k_pass_a", fc.folds ? k_pass_a<SHAPE_OF(sh), true> : k_pass_a<SHAPE_OF(sh)>,
-                               dim3(g.gridA, nf), dim3(NTB), g.ldsA * 4, s, g, params, x, at(ws, L.s), at(ws, L.v),
-                               at(ws, L.partA), fa, fc)) return r;
-        if (only < 0 || only == 1)
-            return launch(KID_B, "k_pass_b", fc.folds ? k_pass_b<SHAPE_OF(sh), true> : k_pass_b<SHAPE_OF(sh)>,
-                          dim3(g.gridS, nf), dim3(NTB), g.ldsB * 4, s, g, params, at(ws, L.coef), at(ws, L.v), m2,
-                          at(ws, L.d2), at(ws, L.E1), at(ws, L.E2), at(ws, L.q3), at(ws, L.r3), at(ws, L.partB),
-                          fb, fc);
+        if (c.only < 0 || c.only == TK_A)
+            if (int r = launch(KID_A, "k_pass_a", fold ? k_pass_a<SHAPE_OF(sh), true> : k_pass_a<SHAPE_OF(sh)>,
+                               dim3(g.gridA, c.nf), dim3(NTB), g.ldsA * 4, c.s, g, c.params, c.x, c.at(L.s), c.at(L.v),
+                               c.at(L.partA), pass_fin(g, c, TK_A), c.fc)) return r;
+        if (c.only < 0 || c.only == TK_B)
+            return launch(KID_B, "k_pass_b", fold ? k_pass_b<SHAPE_OF(sh), true> : k_pass_b<SHAPE_OF(sh)>,
+                          dim3(g.gridS, c.nf), dim3(NTB), g.ldsB * 4, c.s, g, c.params, c.at(L.coef), c.at(L.v), c.m2,
+                          c.at(L.d2), c.at(L.E1), c.at(L.E2), c.at(L.q3), c.at(L.r3), c.at(L.partB),
+                          pass_fin(g, c, TK_B), c.fc);
         return 0;
     });
 }
 
-// adam: nullptr = gradients only
-static int run_backward(const Geo& g, const WsLayout& L, char* ws, float* params,
-                        const float* x, const uint8_t* m2, const uint8_t* m3, const float* dlogits,
-                        const int64_t* labels, float* logits, float* grads, float* loss, int c_mode,
-                        const FinArgs* adam, hipStream_t s, const FoldCall& fc = FoldCall{}, int nf = 1,
-                        int only = -1) {
-    if (g.wide)
-        return run_backward_wide(g, L, ws, params, x, m2, m3, dlogits, labels, logits, grads, loss, c_mode, adam, s);
-    const float* coef = (const float*)(ws + L.coef);
-    const float* dl = dlogits ? dlogits : (const float*)(ws + L.dl);
-    const FinArgs fcC = fin_args(L, ws, TK_C, nullptr, grads, loss, 0, (c_mode & PC_CE) ? 1 : 0);
-    const FinArgs fd = fin_args(L, ws, TK_D, nullptr, grads, nullptr, 0, 0);
-    FinArgs fe = fin_args(L, ws, TK_E, nullptr, grads, nullptr, 0, 0);
-    if (adam) attach_adam(&fe, params, *adam);
+// passes C, D and E
+static int run_backward(const Geo& g, const StepCall& c) {
+    if (g.wide) return run_backward_wide(g, c);
+    const WsOff& L = c.off;
+    const bool fold = c.fc.folds;
+    const float* dl = c.dlogits ? c.dlogits : c.at(L.dl);
+    if (c.only < 0 || c.only == TK_C)
+        if (int r = run_pass_c(g, c)) return r;
     return dispatch_shape(g, [&](auto sh) {
-        if (only < 0 || only == 2)
-            if (int r = launch(KID_C, "k_pass_c(bwd)", fc.folds ? k_pass_c<SHAPE_OF(sh), true> : k_pass_c<SHAPE_OF(sh)>,
-                               dim3(g.grid, nf), dim3(64 * g.nwC), g.ldsC * 4, s, g, params, coef, at(ws, L.r3), m3,
-                               dlogits, labels, logits, at(ws, L.dl), at(ws, L.partC), c_mode, fcC, fc)) return r;
-        if (only < 0 || only == 3) {
+        if (c.only < 0 || c.only == TK_D) {
             // fold launches and the device generator run the instantiation without the host-mask path
             // (the profile label and the error string stay "k_pass_d": bench and tests match on them)
-            auto k = fc.folds ? k_pass_dr<SHAPE_OF(sh), true, false>
-                   : (m2 || m3) ? k_pass_dr<SHAPE_OF(sh)> : k_pass_dr<SHAPE_OF(sh), false, false>;
-            if (int r = launch(KID_D, "k_pass_d", k, dim3(g.gridS, nf), dim3(NTB), g.ldsD * 4, s, g, params, coef,
-                               at(ws, L.d2), at(ws, L.E1), at(ws, L.E2), at(ws, L.q3), at(ws, L.r3), m2, m3, dl,
-                               at(ws, L.dp2), at(ws, L.partD), fd, fc)) return r;
+            auto k = fold ? k_pass_dr<SHAPE_OF(sh), true, false>
+                   : (c.m2 || c.m3) ? k_pass_dr<SHAPE_OF(sh)> : k_pass_dr<SHAPE_OF(sh), false, false>;
+            if (int r = launch(KID_D, "k_pass_d", k, dim3(g.gridS, c.nf), dim3(NTB), g.ldsD * 4, c.s, g, c.params,
+                               c.at(L.coef), c.at(L.d2), c.at(L.E1), c.at(L.E2), c.at(L.q3), c.at(L.r3), c.m2, c.m3, dl,
+                               c.at(L.dp2), c.at(L.partD), pass_fin(g, c, TK_D), c.fc)) return r;
         }
-        if (only < 0 || only == 4)
-            return launch(KID_E, "k_pass_e", fc.folds ? k_pass_e<SHAPE_OF(sh), true> : k_pass_e<SHAPE_OF(sh)>,
-                          dim3(g.gridE, nf), dim3(NTB), g.ldsE * 4, s, g, params, coef, x, at(ws, L.s), at(ws, L.v),
-                          at(ws, L.dp2), at(ws, L.partE), fe, fc);
+        if (c.only < 0 || c.only == TK_E)
+            return launch(KID_E, "k_pass_e", fold ? k_pass_e<SHAPE_OF(sh), true> : k_pass_e<SHAPE_OF(sh)>,
+                          dim3(g.gridE, c.nf), dim3(NTB), g.ldsE * 4, c.s, g, c.params, c.at(L.coef), c.x, c.at(L.s),
+                          c.at(L.v), c.at(L.dp2), c.at(L.partE), pass_fin(g, c, TK_E), c.fc);
         return 0;
     });
 }
@@ -482,6 +497,11 @@ static int check_ptrs(const void* a, const char* na, const void* b = (const void
     if (!a) return fail(EEGNET_EINVAL, "%s is NULL", na);
     if (!b) return fail(EEGNET_EINVAL, "%s is NULL", nb);
     return 0;
+}
+
+// flags outside `known` are refused, in the entry point's words (`fmt` takes the unknown bits as %x)
+static int check_flags(int flags, int known, const char* fmt) {
+    return (flags & ~known) ? fail(EEGNET_EINVAL, fmt, flags & ~known) : 0;
 }
 
 // geometry of an entry point the F2 > 16 path does not implement: wide dims are refused before the wide
@@ -527,7 +547,8 @@ int eegnet_workspace_bytes(const eegnet_dims* dims, size_t* out) {
     Geo g;
     if (int r = make_geo(dims, &g)) return r;
     if (!out) return fail(EEGNET_EINVAL, "out is NULL");
-    *out = make_layout(g).total;
+    WsOff L;
+    *out = make_layout(g, L);
     return 0;
 }
 
@@ -543,22 +564,12 @@ int eegnet_forward_train(const eegnet_dims* dims, const float* params, float* bn
     if (int r = check_ptrs(ws, "ws")) return r;
     set_key(&g, seed, offset);
     ensure_attrs();
-    const WsLayout L = make_layout(g);
-    hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)ws;
-    if (int r = run_forward(g, L, w, params, bn_buffers, x, mask2, 1, num_batches_tracked, s)) return r;
-    FinArgs none;
-    memset(&none, 0, sizeof(none));
-    // pass C for the logits alone: no labels, no dlogits, no partial rows
-    if (g.wide)
-        return launch(KID_WC, "k_wpass_c(fwd)", spec_w5(g) ? k_wpass_c<NTB2, true> : k_wpass_c<NTB2>,
-                      dim3(g.gridW2), dim3(NTB2), g.ldsWC * 4, s, g, params, at(w, L.coef), at(w, L.r3), mask3, nullptr,
-                      nullptr, logits, nullptr, nullptr, PC_LOGITS, none);
-    return dispatch_shape(g, [&](auto sh) {
-        return launch(KID_C, "k_pass_c(fwd)", k_pass_c<SHAPE_OF(sh)>, dim3(g.grid), dim3(64 * g.nwC), g.ldsC * 4, s, g,
-                      params, at(w, L.coef), at(w, L.r3), mask3, nullptr, nullptr, logits, nullptr, nullptr, PC_LOGITS,
-                      none, FoldCall{});
-    });
+    StepCall c(g, ws, stream);
+    c.params = params; c.bn = bn_buffers; c.x = x; c.m2 = mask2; c.m3 = mask3;
+    c.logits = logits; c.nbt = num_batches_tracked;
+    c.c_mode = PC_LOGITS;                 // pass C for the logits alone: no labels, no dlogits
+    if (int r = run_forward(g, c)) return r;
+    return run_pass_c(g, c);
 }
 
 int eegnet_backward(const eegnet_dims* dims, const float* params, const float* x,
@@ -574,11 +585,11 @@ int eegnet_backward(const eegnet_dims* dims, const float* params, const float* x
     if (!dlogits && !labels) return fail(EEGNET_EINVAL, "need dlogits or labels");
     set_key(&g, seed, offset);
     ensure_attrs();
-    const WsLayout L = make_layout(g);
-    const int mode = PC_BWD | (dlogits ? 0 : PC_CE);
-    hipStream_t s = (hipStream_t)stream;
-    float* p = const_cast<float*>(params);        // written only by a fused Adam, which this call has not
-    return run_backward(g, L, (char*)ws, p, x, mask2, mask3, dlogits, labels, nullptr, grads, loss, mode, nullptr, s);
+    StepCall c(g, ws, stream);
+    c.params = params; c.x = x; c.m2 = mask2; c.m3 = mask3;
+    c.dlogits = dlogits; c.labels = labels; c.grads = grads; c.loss = loss;
+    c.c_mode = PC_BWD | (dlogits ? 0 : PC_CE);
+    return run_backward(g, c);
 }
 
 int eegnet_forward_eval(const eegnet_dims* dims, const float* params, const float* bn_buffers,
@@ -676,21 +687,20 @@ int eegnet_train_step(const eegnet_dims* dims, float* params, float* bn_buffers,
     if (int r = check_ptrs(x, "x", labels, "labels")) return r;
     if (int r = check_ptrs(grads, "grads", ws, "ws")) return r;
     if (adam_state && !step) return fail(EEGNET_EINVAL, "step is NULL");
-    if (flags & ~(EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP))
-        return fail(EEGNET_EINVAL, "unknown flags 0x%x (bit 4, round 5's opt-in persistent step, is retired)",
-                    flags & ~(EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP));
+    if (int r = check_flags(flags, EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP,
+                            "unknown flags 0x%x (bit 4, round 5's opt-in persistent step, is retired)")) return r;
     if (int r = train_flags(&g, flags, seed, offset, step)) return r;
     ensure_attrs();
-    const WsLayout L = make_layout(g);
-    hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)ws;
-    if (int r = run_forward(g, L, w, params, bn_buffers, x, nullptr, 1, num_batches_tracked, s)) return r;
-    const int mode = PC_BWD | PC_CE | (logits ? PC_LOGITS : 0);
+    StepCall c(g, ws, stream);
+    c.params = params; c.bn = bn_buffers; c.x = x; c.labels = labels;
+    c.logits = logits; c.grads = grads; c.loss = loss; c.nbt = num_batches_tracked;
+    c.c_mode = PC_BWD | PC_CE | (logits ? PC_LOGITS : 0);
     // Adam runs in pass E's finalize; adam_state == NULL: gradients only (data-parallel: all-reduce,
     // clamp, then eegnet_adam_step)
-    const FinArgs adam = adam_args(adam_state, g.nparam, step, lr, beta1, beta2, eps);
-    return run_backward(g, L, w, params, x, nullptr, nullptr, nullptr, labels, logits, grads, loss, mode,
-                        adam_state ? &adam : nullptr, s);
+    c.adam = adam_state != nullptr;
+    c.adam_state = adam_state; c.step = step; c.lr = lr; c.b1 = beta1; c.b2 = beta2; c.eps = eps;
+    if (int r = run_forward(g, c)) return r;
+    return run_backward(g, c);
 }
 
 // One stage of a data-parallel train step with synchronised BatchNorm (distributed.py
@@ -716,30 +726,19 @@ int eegnet_train_stage(const eegnet_dims* dims, int stage, int64_t norm_batch, f
     g.Bn = (int)norm_batch;
     if (int r = train_flags(&g, flags, seed, offset, step)) return r;
     ensure_attrs();
-    const WsLayout L = make_layout(g);
-    hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)ws;
     const int pass = stage >> 1;
+    const bool fin = stage & 1;
     g.defer = 1;                  // (k_fin: fin5 runs the whole Adam update, adam_early is off)
-    if ((stage & 1) == 0) {
-        if (pass < 2)
-            return run_forward(g, L, w, params, bn_buffers, x, nullptr, 1, num_batches_tracked, s, FoldCall{}, 1, pass);
-        return run_backward(g, L, w, params, x, nullptr, nullptr, nullptr, labels, nullptr, grads, loss, PC_BWD | PC_CE,
-                            nullptr, s, FoldCall{}, 1, pass);
-    }
-    FinArgs fa;
-    int ncols, lds;
-    switch (pass) {
-        case 0: fa = fin_args(L, w, TK_A, bn_buffers, nullptr, nullptr, 1, 0); ncols = g.nA; lds = g.ldsA; break;
-        case 1: fa = fin_args(L, w, TK_B, bn_buffers, nullptr, nullptr, 1, 0, num_batches_tracked); ncols = g.nB; lds = g.ldsB; break;
-        case 2: fa = fin_args(L, w, TK_C, nullptr, grads, loss, 0, 1); ncols = g.nC; lds = g.ldsC; break;
-        case 3: fa = fin_args(L, w, TK_D, nullptr, grads, nullptr, 0, 0); ncols = g.nD; lds = g.ldsD; break;
-        default:
-            fa = fin_args(L, w, TK_E, nullptr, grads, nullptr, 0, 0); ncols = g.nE; lds = g.ldsE;
-            if (adam_state) attach_adam(&fa, params, adam_args(adam_state, g.nparam, step, lr, beta1, beta2, eps));
-            break;
-    }
-    return launch(KID_NONE, "k_fin", k_fin, dim3(1), dim3(NTB), (size_t)lds * 4, s, g, params, fa, pass, ncols);
+    StepCall c(g, ws, stream);
+    c.params = params; c.bn = bn_buffers; c.x = x; c.labels = labels;
+    c.grads = grads; c.loss = loss; c.nbt = num_batches_tracked;
+    c.c_mode = PC_BWD | PC_CE;
+    c.adam = fin && adam_state;   // Adam is the finalize stage's; the pass is launched for its gradients only
+    c.adam_state = adam_state; c.step = step; c.lr = lr; c.b1 = beta1; c.b2 = beta2; c.eps = eps;
+    c.only = pass;
+    if (!fin) return pass <= TK_B ? run_forward(g, c) : run_backward(g, c);
+    return launch(KID_NONE, "k_fin", k_fin, dim3(1), dim3(NTB), (size_t)(g.*kPass[pass].lds) * 4, c.s, g, params,
+                  pass_fin(g, c, pass), pass, g.*kPass[pass].ncols);
 }
 
 // where stage 2k leaves pass k's sums in a workspace: byte offset and count of fp64 values
@@ -748,10 +747,10 @@ int eegnet_stage_sums(const eegnet_dims* dims, int pass, size_t* offset_bytes, i
     if (int r = make_geo(dims, &g)) return r;
     if (pass < 0 || pass >= TK_COUNT) return fail(EEGNET_EINVAL, "pass must be in [0, %d) (got %d)", TK_COUNT, pass);
     if (!offset_bytes || !count) return fail(EEGNET_EINVAL, "null output pointer");
-    const WsLayout L = make_layout(g);
+    WsOff L;
+    make_layout(g, L);
     *offset_bytes = L.sums;
-    const int n[TK_COUNT] = {g.nA, g.nB, g.nC, g.nD, g.nE};
-    *count = n[pass];
+    *count = g.*kPass[pass].ncols;
     return 0;
 }
 
@@ -804,6 +803,20 @@ static int frozen_offset(const Geo& g, int train_from, int* off) {
                 "EEGNET_TRAIN_FROM_BLOCK2 (2) or EEGNET_TRAIN_FROM_CLASSIFIER (3) (got %d)", train_from);
 }
 
+// The arguments every fold-indexed step takes, checked, as the kernels' FoldCall; `off`, the workspace
+// layout of the five-pass step, stays zero for the caller to assign.
+static int fold_call(FoldCall* fc, int nfolds, const eegnet_fold* folds, int64_t row0, int64_t slot, uint64_t offset,
+                     float lr, float beta1, float beta2, float eps) {
+    if (nfolds < 1 || nfolds > 65535) return fail(EEGNET_EINVAL, "nfolds must be in [1, 65535] (got %d)", nfolds);
+    if (!folds) return fail(EEGNET_EINVAL, "folds is NULL");
+    if (row0 < 0 || slot < 0) return fail(EEGNET_EINVAL, "row0 / slot must be >= 0");
+    memset(fc, 0, sizeof(*fc));
+    fc->folds = folds;
+    fc->row0 = row0; fc->slot = slot; fc->koff = offset;
+    fc->lr = lr; fc->b1 = beta1; fc->b2 = beta2; fc->eps = eps;
+    return 0;
+}
+
 // workgroups of k_frozen_reduce: FR_OUT outputs each over the gradients from `off` on and the loss
 static unsigned frozen_reduce_grid(const Geo& g, int off = 0) {
     return (unsigned)((g.nparam - off + 1 + FR_OUT - 1) / FR_OUT);
@@ -848,8 +861,7 @@ int eegnet_frozen_step_from(const eegnet_dims* dims, float* params, const float*
     if (!dlogits && !labels) return fail(EEGNET_EINVAL, "frozen step: need dlogits or labels");
     if (dlogits && labels) return fail(EEGNET_EINVAL, "frozen step: dlogits and labels are exclusive");
     if (adam_state && !step) return fail(EEGNET_EINVAL, "step is NULL");
-    if (flags & ~(EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP))
-        return fail(EEGNET_EINVAL, "frozen step: unknown flags 0x%x", flags & ~(EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP));
+    if (int r = check_flags(flags, EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP, "frozen step: unknown flags 0x%x")) return r;
     if ((g.T & 3) == 0 && ((uintptr_t)x & 15)) return fail(EEGNET_EINVAL, "frozen BatchNorm: x must be 16-byte aligned");
     if (int r = train_flags(&g, flags, seed, offset, step)) return r;
     ensure_attrs();
@@ -898,20 +910,13 @@ int eegnet_frozen_step_folds_from(const eegnet_dims* dims, int nfolds, const eeg
     if (int r = frozen_geo(dims, &g)) return r;
     int off;
     if (int r = frozen_offset(g, train_from, &off)) return r;
-    if (nfolds < 1 || nfolds > 65535) return fail(EEGNET_EINVAL, "nfolds must be in [1, 65535] (got %d)", nfolds);
-    if (!folds) return fail(EEGNET_EINVAL, "folds is NULL");
-    if (row0 < 0 || slot < 0) return fail(EEGNET_EINVAL, "row0 / slot must be >= 0");
-    if (flags & ~EEGNET_NO_CLAMP)
-        return fail(EEGNET_EINVAL, "frozen fold step: unknown flags 0x%x (the dropout keys always follow the "
-                    "folds' device steps)", flags & ~EEGNET_NO_CLAMP);
+    FoldCall fc;
+    if (int r = fold_call(&fc, nfolds, folds, row0, slot, offset, lr, beta1, beta2, eps)) return r;
+    if (int r = check_flags(flags, EEGNET_NO_CLAMP, "frozen fold step: unknown flags 0x%x (the dropout keys always "
+                            "follow the folds' device steps)")) return r;
     g.noclamp = (flags & EEGNET_NO_CLAMP) ? 1 : 0;
     set_key(&g, 0, offset);                           // the keep threshold (keys come per fold)
     ensure_attrs();
-    FoldCall fc;
-    memset(&fc, 0, sizeof(fc));
-    fc.folds = folds;
-    fc.row0 = row0; fc.slot = slot; fc.koff = offset;
-    fc.lr = lr; fc.b1 = beta1; fc.b2 = beta2; fc.eps = eps;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nf = (unsigned)nfolds;
     const FzFold<true> fold{fc};
@@ -954,9 +959,6 @@ int eegnet_frozen_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_f
 #ifndef EEGNET_FOLD_TPW_C
 #define EEGNET_FOLD_TPW_C 16
 #endif
-static void fold_tpw(int* s, int* c) {
-    *s = EEGNET_FOLD_TPW_S; *c = EEGNET_FOLD_TPW_C;
-}
 
 // The per-fold grids of a fold-indexed launch.  The folds share the chip: each workgroup runs several
 // trials of its fold (its prologue and the reduction tail are per workgroup).  The per-fold grid is a
@@ -965,12 +967,11 @@ static void fold_tpw(int* s, int* c) {
 // (fold-batch width, sharding over ranks).  Capped at the non-fold grids the workspace's partial rows
 // are sized for.
 static void fold_grids(Geo* g) {
-    int tpwS, tpwC;
-    fold_tpw(&tpwS, &tpwC);
-    g->gridA = std::max(1, std::min(g->gridS, (g->B + EEGNET_FOLD_TPW_A - 1) / EEGNET_FOLD_TPW_A));
-    g->gridE = std::max(1, std::min(g->gridS, (g->B + EEGNET_FOLD_TPW_E - 1) / EEGNET_FOLD_TPW_E));
-    g->gridS = std::max(1, std::min(g->gridS, (g->B + tpwS - 1) / tpwS));
-    g->grid = std::max(1, std::min(g->grid, (g->B + tpwC - 1) / tpwC));
+    const auto split = [&](int cap, int tpw) { return std::max(1, std::min(cap, (g->B + tpw - 1) / tpw)); };
+    g->gridA = split(g->gridS, EEGNET_FOLD_TPW_A);
+    g->gridE = split(g->gridS, EEGNET_FOLD_TPW_E);
+    g->gridS = split(g->gridS, EEGNET_FOLD_TPW_S);
+    g->grid = split(g->grid, EEGNET_FOLD_TPW_C);
 }
 
 // the three launches of eegnet_ems on rows of T: chunk aggregates, carries, output; scratch holds the
@@ -1015,27 +1016,16 @@ int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fo
     Geo g;
     if (int r = make_geo(dims, &g)) return r;
     if (g.wide) return fail(EEGNET_EINVAL, "eegnet_train_step_folds: F1*D = %d > 16 is not supported", g.F2);
-    if (nfolds < 1 || nfolds > 65535) return fail(EEGNET_EINVAL, "nfolds must be in [1, 65535] (got %d)", nfolds);
-    if (!folds) return fail(EEGNET_EINVAL, "folds is NULL");
-    if (row0 < 0 || slot < 0) return fail(EEGNET_EINVAL, "row0 / slot must be >= 0");
+    StepCall c(g, nullptr, stream);                   // no workspace: every per-fold pointer comes from `folds`
+    if (int r = fold_call(&c.fc, nfolds, folds, row0, slot, offset, lr, beta1, beta2, eps)) return r;
+    c.fc.off = c.off;                                 // (laid out for the non-fold grids, fold_grids' caps)
+    c.nf = nfolds;
+    c.c_mode = PC_BWD | PC_CE;
     set_key(&g, 0, offset);                           // the keep threshold (keys come per fold)
     ensure_attrs();
-    const WsLayout L = make_layout(g);
     fold_grids(&g);
-    FoldCall fc;
-    memset(&fc, 0, sizeof(fc));
-    fc.folds = folds;
-    fc.row0 = row0; fc.slot = slot; fc.koff = offset;
-    fc.lr = lr; fc.b1 = beta1; fc.b2 = beta2; fc.eps = eps;
-    fc.off = {L.cnt, L.partA, L.partB, L.partC, L.partD, L.partE, L.sums, L.stats, L.coef, L.d2, L.E1, L.E2,
-              L.dp2, L.dl, L.s, L.v, L.q3, L.r3};
-    hipStream_t s = (hipStream_t)stream;
-    FinArgs adam;                                     // non-null marker: pass E's finalize runs Adam
-    memset(&adam, 0, sizeof(adam));
-    char* w = nullptr;                                // every per-fold pointer comes from `folds`
-    if (int r = run_forward(g, L, w, nullptr, nullptr, nullptr, nullptr, 1, nullptr, s, fc, nfolds)) return r;
-    return run_backward(g, L, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        PC_BWD | PC_CE, &adam, s, fc, nfolds);
+    if (int r = run_forward(g, c)) return r;
+    return run_backward(g, c);
 }
 
 int eegnet_eval_folds(const eegnet_dims* dims, int nfolds, const eegnet_eval_fold* folds, int64_t max_n,

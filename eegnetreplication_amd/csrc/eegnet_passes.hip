@@ -121,7 +121,7 @@ __device__ __forceinline__ void pass_c_body(const Geo& g, const float* __restric
         perm = f.perm; row0 = fc.row0;
         dlout = (float*)(ws + fc.off.dl);
         part = (float*)(ws + fc.off.partC);
-        fa = fold_fin(fc, f, TK_C, 0, 1, false, false, g.nparam);
+        fa = fold_fin<TK_C>(fc, f, g.nparam);
         dk1 = fold_drop_key(fc, f, 1);
     } else {
         dk1 = drop_key(g, 1);
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(NTB, TT ? WPEB : 2) void k_pass_dr(Geo g, const flo
         dl = (const float*)(ws + fc.off.dl);
         dp2g = (float*)(ws + fc.off.dp2);
         part = (float*)(ws + fc.off.partD);
-        fa = fold_fin(fc, f, TK_D, 0, 0, false, false, g.nparam);
+        fa = fold_fin<TK_D>(fc, f, g.nparam);
         dk0 = fold_drop_key(fc, f, 0);
         dk1 = fold_drop_key(fc, f, 1);
     } else {

@@ -255,7 +255,7 @@ __device__ __forceinline__ void pass_a_body(const Geo& g, const float* __restric
         sg = (float*)((char*)f.ws + fc.off.s);
         vg = (float*)((char*)f.ws + fc.off.v);
         part = (float*)((char*)f.ws + fc.off.partA);
-        fa = fold_fin(fc, f, TK_A, 1, 0, false, false, g.nparam);
+        fa = fold_fin<TK_A>(fc, f, g.nparam);
     }
     // every pass re-arms its own tickets when it finishes; pass A also clears those of the later
     // passes of this call (stream order), so a call never depends on how the previous one ended
@@ -805,7 +805,7 @@ __device__ __forceinline__ void pass_b_body(const Geo& g, const float* __restric
         d2g = (float*)(ws + fc.off.d2); E1g = (float*)(ws + fc.off.E1); E2g = (float*)(ws + fc.off.E2);
         q3g = (float*)(ws + fc.off.q3); r3g = (float*)(ws + fc.off.r3);
         part = (float*)(ws + fc.off.partB);
-        fa = fold_fin(fc, f, TK_B, 1, 0, true, false, g.nparam);
+        fa = fold_fin<TK_B>(fc, f, g.nparam);
         dk0 = fold_drop_key(fc, f, 0);
     } else {
         dk0 = drop_key(g, 0);
@@ -1050,7 +1050,7 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
         vg = (const float*)(ws + fc.off.v);
         dp2g = (const float*)(ws + fc.off.dp2);
         part = (float*)(ws + fc.off.partE);
-        fa = fold_fin(fc, f, TK_E, 0, 0, false, true, g.nparam);
+        fa = fold_fin<TK_E>(fc, f, g.nparam);
     }
     constexpr int NTS = FF ? 1 : RPW;
     const int D = FF ? 2 : g.D;

@@ -268,3 +268,124 @@ def test_retired_persist_flag_is_rejected():
         assert b"unknown flags" in lib.eegnet_last_error()
     hdr = open(os.path.join(ROOT, "include", "eegnet_abi.h")).read()
     assert "EEGNET_PERSIST" not in hdr
+
+
+# ---- the argument checks of the five train entry points and eegnet_stage_sums, one table ----
+_NARROW = dict(B=8, C=3, T=64)
+_WIDE = dict(B=8, C=5, T=72, F1=8, D=4, K1=32)
+# entry point -> (its required pointers in the order the library checks them, every pointer a caller
+# may pass, F1*D > 16 accepted).  The call builders below take {pointer name: address or None}.
+_TRAIN_ENTRY_POINTS = {
+    "eegnet_forward_train": (("params", "bn_buffers", "x", "logits", "ws"), ("mask2", "mask3", "nbt"), True),
+    "eegnet_backward": (("params", "x", "grads", "ws"), ("dlogits", "labels", "mask2", "mask3", "loss"), True),
+    "eegnet_train_step": (("params", "bn_buffers", "x", "labels", "grads", "ws"),
+                          ("adam_state", "step", "loss", "logits", "nbt"), True),
+    "eegnet_train_stage": (("params", "bn_buffers", "x", "labels", "grads", "ws"),
+                           ("adam_state", "step", "loss", "nbt"), False),
+    "eegnet_train_step_folds": (("folds",), (), False),
+}
+
+
+def _train_call(lib, name, d, p, flags=0, stage=0, norm_batch=None, nfolds=2, row0=0, slot=0):
+    """One call of a train entry point with the pointers of `p` (a missing name is NULL)."""
+    import ctypes
+    g = lambda k: p.get(k)
+    dd = ctypes.byref(d)
+    if name == "eegnet_forward_train":
+        return lib.eegnet_forward_train(dd, g("params"), g("bn_buffers"), g("x"), g("mask2"), g("mask3"), 1, 2,
+                                        g("logits"), g("ws"), None, g("nbt"))
+    if name == "eegnet_backward":
+        return lib.eegnet_backward(dd, g("params"), g("x"), g("dlogits"), g("labels"), g("mask2"), g("mask3"), 1, 2,
+                                   g("grads"), g("loss"), g("ws"), None, flags)
+    if name == "eegnet_train_step":
+        return lib.eegnet_train_step(dd, g("params"), g("bn_buffers"), g("x"), g("labels"), 1, 2, g("grads"),
+                                     g("adam_state"), g("step"), 1e-3, 0.9, 0.999, 1e-7, g("loss"), g("logits"),
+                                     g("ws"), None, flags, g("nbt"))
+    if name == "eegnet_train_stage":
+        return lib.eegnet_train_stage(dd, stage, d.B if norm_batch is None else norm_batch, g("params"),
+                                      g("bn_buffers"), g("x"), g("labels"), 1, 2, g("grads"), g("adam_state"),
+                                      g("step"), 1e-3, 0.9, 0.999, 1e-7, g("loss"), g("ws"), None, flags, g("nbt"))
+    assert name == "eegnet_train_step_folds"
+    return lib.eegnet_train_step_folds(dd, nfolds, g("folds"), row0, slot, 3, 1e-3, 0.9, 0.999, 1e-7, None)
+
+
+def test_train_entry_points_name_the_argument_they_refuse():
+    """The argument checks of eegnet_forward_train, eegnet_backward, eegnet_train_step, eegnet_train_stage
+    and eegnet_train_step_folds at a narrow and a wide shape: with every pointer a dummy address and exactly
+    one required pointer NULL the call returns -1 and eegnet_last_error names that pointer; with all of them
+    NULL it names the first one the library checks.  The stage and fold entry points refuse F1*D > 16 before
+    they look at a pointer.  Then the checks beside the pointers, and eegnet_stage_sums against the
+    partial-row lengths of the five passes.  Every call leaves an argument invalid (the checks precede every
+    device call) or is a geometry query: nothing is launched, no GPU is needed."""
+    import ctypes
+    from eegnetreplication_amd import _lib, ops
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libeegnet_hip.so not built")
+    lib = _lib.load()
+    err = lambda: lib.eegnet_last_error().decode()
+    dummy = 4096                                     # never dereferenced: every call fails on an argument
+    for kw in (_NARROW, _WIDE):
+        d = _lib.dims(**kw)
+        wide = d.F1 * d.D > 16
+        for name, (required, optional, takes_wide) in _TRAIN_ENTRY_POINTS.items():
+            every = {k: dummy for k in required + optional}
+            patterns = [({k: v for k, v in every.items() if k != miss}, miss) for miss in required]
+            patterns.append(({}, required[0]))
+            for p, named in patterns:
+                assert _train_call(lib, name, d, p) == -1, (name, kw, named)
+                if wide and not takes_wide:
+                    assert err() == f"{name}: F1*D = {d.F1 * d.D} > 16 is not supported", (name, named)
+                else:
+                    assert err() == f"{named} is NULL", (name, kw, named)
+
+    d = _lib.dims(**_NARROW)
+    full = lambda name: {k: dummy for k in sum(_TRAIN_ENTRY_POINTS[name][:2], ())}
+    without = lambda name, *ks: {k: v for k, v in full(name).items() if k not in ks}
+    for kw in (_NARROW, _WIDE):
+        assert _train_call(lib, "eegnet_backward", _lib.dims(**kw), without("eegnet_backward", "dlogits", "labels")) == -1
+        assert err() == "need dlogits or labels"
+    for name in ("eegnet_train_step", "eegnet_train_stage"):
+        assert _train_call(lib, name, d, without(name, "step")) == -1
+        assert err() == "step is NULL", name
+        assert _train_call(lib, name, d, without(name, "step", "adam_state"), flags=ops.KEY_FROM_STEP) == -1
+        assert err() == "EEGNET_KEY_FROM_STEP needs the device step counter", name
+    for stage in (-1, 10):
+        assert _train_call(lib, "eegnet_train_stage", d, full("eegnet_train_stage"), stage=stage) == -1
+        assert err() == f"stage must be in [0, 10) (got {stage})"
+    assert _train_call(lib, "eegnet_train_stage", d, full("eegnet_train_stage"), norm_batch=d.B - 1) == -1
+    assert err() == f"norm_batch must be in [B, 2^30] (got {d.B - 1})"
+    folds = {"folds": dummy}
+    for nfolds in (0, 65536):
+        assert _train_call(lib, "eegnet_train_step_folds", d, folds, nfolds=nfolds) == -1
+        assert err() == f"nfolds must be in [1, 65535] (got {nfolds})"
+    assert _train_call(lib, "eegnet_train_step_folds", d, {}) == -1
+    assert err() == "folds is NULL"
+    for bad in (dict(row0=-1), dict(slot=-1)):
+        assert _train_call(lib, "eegnet_train_step_folds", d, folds, **bad) == -1
+        assert err() == "row0 / slot must be >= 0"
+
+    # eegnet_stage_sums: pass k's count is the length of its partial row (eegnet_geometry.h, the part-row
+    # comments of the pass kernels); the head of pass A's row is what eegnet_x_stats_width reports
+    off, cnt = ctypes.c_size_t(0), ctypes.c_int(0)
+    sums = lambda dd, k: lib.eegnet_stage_sums(ctypes.byref(dd), k, ctypes.byref(off), ctypes.byref(cnt))
+    for kw in (_NARROW, _WIDE):
+        d = _lib.dims(**kw)
+        for k in (-1, 5):
+            assert sums(d, k) == -1
+            assert err() == f"pass must be in [0, 5) (got {k})"
+        F2, NF = d.F1 * d.D, d.F1 * d.D * (d.T // 32)
+        P = (d.K1 - 1) // 2
+        R = d.K1 - 1 - P
+        head = d.K1 + 1 + R * (R + 1) // 2 + P * (P + 1) // 2 + R + P
+        if F2 <= 16:
+            assert lib.eegnet_x_stats_width(ctypes.byref(d)) == head
+        QR = d.F1 if (F2 <= 16 and d.D == 2) else F2
+        want = (head + 2 * F2, 2 * F2, 4 * NF + 4 + 2 * F2 + 1, F2 * F2 + 18 * F2, QR * d.K1 + F2 * d.C + 2 * F2)
+        offs = set()
+        for k in range(5):
+            assert sums(d, k) == 0, err()
+            assert cnt.value == want[k], (kw, k)
+            offs.add(off.value)
+        assert len(offs) == 1 and 0 < off.value < _lib.workspace_bytes(d)      # one region for every pass
+        assert lib.eegnet_stage_sums(ctypes.byref(d), 0, None, ctypes.byref(cnt)) == -1
+        assert err() == "null output pointer"

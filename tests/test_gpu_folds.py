@@ -5,7 +5,7 @@ fold-indexed launches), so the bar is bit-equality: every fold of a concurrent b
 exactly the parameters, BN buffers, Adam state and loss sums of the same fold trained alone, and a
 one-fold stream batch must reproduce FusedTrainer, whose step is pinned to the oracle and the
 reference golden vectors by tests/test_gpu_parity.py.  A fold-indexed launch splits a fold's batch
-over fewer workgroups than FusedTrainer (by the batch size alone: eegnet_host.hip fold_tpw), so
+over fewer workgroups than FusedTrainer (by the batch size alone: eegnet_host.hip fold_grids), so
 against FusedTrainer it agrees to the fp32 rounding of its partial sums, not bit for bit.
 Shapes follow the real protocol: 22 x 257 trials (02_preprocessing_pipeline.ipynb:1867), batch 64
 with a short last batch (train.py:87, DataLoader drop_last=False).
