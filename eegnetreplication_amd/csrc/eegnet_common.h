@@ -283,6 +283,34 @@ __device__ __forceinline__ void st_pol(V v, V* p) {
     if constexpr (NT != 0) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
+// Cache policy of the step's streamed loads.  x is a new buffer every step, read once by
+// pass A and once by pass E with ~500 MB of other traffic in between: no cache can serve its second read,
+// and loaded under the plain policy it pushes out the s / v lines pass A has just written, which pass B
+// reads next.  So the x loads of the single-model passes A and E carry `nt` (EEGNET_LD_X = LD_NT, the
+// default; LD_DEF builds the plain loads back for an A/B); the fold launches and the F2 > 16 passes re-read
+// x rows and keep the plain policy (x_pol, eegnet_stream.hip).  The planes' own loads stay plain: `nt` on v, s or the block-2
+// planes measured slower, and the sc modifiers on the x DMAs no different from `nt` alone.  Only for data an earlier launch or
+// the host wrote: partial rows, tickets, the coefficient block and the parameters keep their own
+// flavours (pub / ld_pub, ldc), on which their coherence rests.  A policy bit changes neither the issue
+// order nor what vmcnt counts, so no wait window depends on it.
+enum { LD_DEF = 0, LD_NT = 1 };
+#ifndef EEGNET_LD_X
+#define EEGNET_LD_X LD_NT
+#endif
+// a load to registers: the builtin yields `global_load_* ... nt`, and the compiler counts it like any load
+template <int P, typename V>
+__device__ __forceinline__ V ld_pol(const V* p) {
+    static_assert(P == LD_DEF || P == LD_NT, "load policy");
+    if constexpr (P == LD_NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+// the policy as the aux operand of __builtin_amdgcn_global_load_lds (gfx950: nt = 2); the asm DMAs
+// (dma16 / dma4, eegnet_stream.hip) spell the modifier
+template <int P>
+constexpr int ld_dma_aux() {
+    static_assert(P == LD_DEF || P == LD_NT, "load policy");
+    return P == LD_NT ? 2 : 0;
+}
 
 #ifndef EEGNET_PRIO
 #define EEGNET_PRIO 1
@@ -606,7 +634,7 @@ __device__ __forceinline__ void fir8(const float (&w)[NWF], const float (&tap)[K
 
 // ---- x staging: global -> registers (issued a whole trial ahead) -> LDS rows ----
 // PF floats per thread cover one trial: C*T <= NTH*PF.
-template <int PF, int NT = NTH>
+template <int PF, int NT = NTH, int P = LD_DEF>     // P: the loads' cache policy (ld_pol)
 __device__ __forceinline__ void x_prefetch(const float* __restrict__ xb, int C, int T, float (&pf)[PF], int tid) {
     const int n = C * T;
     if ((T & 3) == 0) {
@@ -615,14 +643,19 @@ __device__ __forceinline__ void x_prefetch(const float* __restrict__ xb, int C, 
         for (int j = 0; j < PF / 4; ++j) {
             const int i = tid + NT * j;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (4 * i < n) v = src[i];
+            if constexpr (P == LD_DEF) {
+                if (4 * i < n) v = src[i];
+            } else if (4 * i < n) {
+                const floatx4 u = ld_pol<P>(reinterpret_cast<const floatx4*>(xb) + i);
+                v = make_float4(u[0], u[1], u[2], u[3]);
+            }
             pf[4 * j] = v.x; pf[4 * j + 1] = v.y; pf[4 * j + 2] = v.z; pf[4 * j + 3] = v.w;
         }
     } else {
 #pragma unroll
         for (int j = 0; j < PF; ++j) {
             const int i = tid + NT * j;
-            pf[j] = i < n ? xb[i] : 0.f;
+            pf[j] = i < n ? ld_pol<P>(xb + i) : 0.f;
         }
     }
 }

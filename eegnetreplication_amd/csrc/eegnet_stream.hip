@@ -42,6 +42,7 @@ typedef __attribute__((address_space(1))) void gvoid_t;
 typedef __attribute__((address_space(3))) void lvoid_t;
 // Rows of other lengths (22 x 257, the real recordings) go by 4-byte pieces: 64 samples per wave
 // instruction, the row's last piece on its first T mod 64 lanes only (the pads stay zero).
+template <int P = LD_DEF>                  // P: the cache policy (eegnet_common.h), through the aux operand
 __device__ __forceinline__ void x_dma(const float* __restrict__ xb, int C, int T, int RS, int LP, float* Xs,
                                       int wave, int lane) {
     if ((T & 255) == 0) {
@@ -49,7 +50,7 @@ __device__ __forceinline__ void x_dma(const float* __restrict__ xb, int C, int T
         for (int i = wave; i < C * np; i += NWB) {
             const int c = i / np, p = i - c * np;
             __builtin_amdgcn_global_load_lds((gvoid_t*)(xb + (size_t)c * T + 256 * p + 4 * lane),
-                                             (lvoid_t*)(Xs + c * RS + LP + 256 * p), 16, 0, 0);
+                                             (lvoid_t*)(Xs + c * RS + LP + 256 * p), 16, 0, ld_dma_aux<P>());
         }
     } else {
         const int np = (T + 63) >> 6;                  // 64-sample pieces per row
@@ -57,7 +58,7 @@ __device__ __forceinline__ void x_dma(const float* __restrict__ xb, int C, int T
             const int c = i / np, p = i - c * np;
             if (lane < T - 64 * p)
                 __builtin_amdgcn_global_load_lds((gvoid_t*)(xb + (size_t)c * T + 64 * p + lane),
-                                                 (lvoid_t*)(Xs + c * RS + LP + 64 * p), 4, 0, 0);
+                                                 (lvoid_t*)(Xs + c * RS + LP + 64 * p), 4, 0, ld_dma_aux<P>());
         }
     }
 }
@@ -67,47 +68,64 @@ __device__ __forceinline__ void x_dma(const float* __restrict__ xb, int C, int T
 // prefetch issued ahead of a phase's LDS work into a stall at its first read.  The caller owns the
 // hand-off: the data is read only after a barrier preceded by a vmcnt wait that covers the DMA
 // (__syncthreads(), or barrier_vm<N> with N vector-memory operations issued after it).
+// P is the cache policy (eegnet_common.h), a modifier on the instruction: it changes neither the issue
+// order nor what vmcnt counts.
+#define EEG_DMA_ASM(INSN, MOD)                                                                     \
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t" INSN " %0, off" MOD :: "v"(gsrc), "s"(la) : "memory", "m0")
+#define EEG_DMA_POL(INSN)                                                                          \
+    if constexpr (P == LD_DEF) EEG_DMA_ASM(INSN, "");                                              \
+    else {                                                                                         \
+        static_assert(P == LD_NT, "load policy");                                                  \
+        EEG_DMA_ASM(INSN, " nt");                                                                  \
+    }
+template <int P = LD_DEF>
 __device__ __forceinline__ void dma16(const float* gsrc, const float* ldst) {
     const unsigned la = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)ldst;
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
-                 :: "v"(gsrc), "s"(la) : "memory", "m0");
+    EEG_DMA_POL("global_load_lds_dwordx4");
 }
+template <int P = LD_DEF>
 __device__ __forceinline__ void dma4(const float* gsrc, const float* ldst) {    // 4 bytes per lane
     const unsigned la = (unsigned)(size_t)(const __attribute__((address_space(3))) float*)ldst;
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off"
-                 :: "v"(gsrc), "s"(la) : "memory", "m0");
+    EEG_DMA_POL("global_load_lds_dword");
 }
 // C rows of T samples at row pitch XP (floats) into LDS rows (stride RS, left pad LP).  Rows at a pitch
 // that is a multiple of 4 go in 16-byte units -- 4 [T/4] of them, then T mod 4 dwords -- else in dwords
 // (a 257-sample row at pitch 257 is not 16-byte aligned: five dword DMAs per row instead of two).
+// the policy of a pass's x loads: nt in the single-model step, whose batch is read once per pass; plain in
+// the fold launches, where folds share training sets and re-read each other's x rows (nt there measured
+// 3 % slower on the 90-fold leg)
+template <bool FOLD>
+constexpr int x_pol() { return FOLD ? LD_DEF : EEGNET_LD_X; }
+template <int P>
 __device__ __forceinline__ void x_dma_asm(const float* __restrict__ xb, int C, int T, int XP, int RS, int LP,
                                           float* Xs, int wave, int lane) {
     if ((T & 255) == 0 && (XP & 3) == 0) {
         const int np = T >> 8;
         for (int i = wave; i < C * np; i += NWB) {
             const int c = i / np, p = i - c * np;
-            dma16(xb + (size_t)c * XP + 256 * p + 4 * lane, Xs + c * RS + LP + 256 * p);
+            dma16<P>(xb + (size_t)c * XP + 256 * p + 4 * lane, Xs + c * RS + LP + 256 * p);
         }
     } else if ((XP & 3) == 0) {
         const int nu = T >> 2, np = (nu + 63) >> 6, nt = T & 3, per = np + (nt ? 1 : 0);
         for (int i = wave; i < C * per; i += NWB) {
             const int c = i / per, p = i - c * per;
             if (p < np) {
-                if (lane < nu - 64 * p) dma16(xb + (size_t)c * XP + 256 * p + 4 * lane, Xs + c * RS + LP + 256 * p);
+                if (lane < nu - 64 * p) dma16<P>(xb + (size_t)c * XP + 256 * p + 4 * lane, Xs + c * RS + LP + 256 * p);
             } else if (lane < nt) {
-                dma4(xb + (size_t)c * XP + 4 * nu + lane, Xs + c * RS + LP + 4 * nu);
+                dma4<P>(xb + (size_t)c * XP + 4 * nu + lane, Xs + c * RS + LP + 4 * nu);
             }
         }
     } else {
         const int np = (T + 63) >> 6;
         for (int i = wave; i < C * np; i += NWB) {
             const int c = i / np, p = i - c * np;
-            if (lane < T - 64 * p) dma4(xb + (size_t)c * XP + 64 * p + lane, Xs + c * RS + LP + 64 * p);
+            if (lane < T - 64 * p) dma4<P>(xb + (size_t)c * XP + 64 * p + lane, Xs + c * RS + LP + 64 * p);
         }
     }
 }
+template <int P = LD_DEF>
 __device__ __forceinline__ void flat_dma_asm(const float* __restrict__ src, int n, float* dst, int wave, int lane) {
-    for (int i = wave; i < (n >> 8); i += NWB) dma16(src + 256 * i + 4 * lane, dst + 256 * i);
+    for (int i = wave; i < (n >> 8); i += NWB) dma16<P>(src + 256 * i + 4 * lane, dst + 256 * i);
 }
 
 // Zero the workgroup's LDS rows [0, n) before the first trial.  With LDS-DMA staging (SKIPX) the x
@@ -141,9 +159,11 @@ __device__ __forceinline__ void zero_pads(float* sm, int nrows, int RS, int LP, 
 }
 
 // LDS-DMA of n floats (n % 256 == 0, 16-byte aligned source) into a contiguous LDS array
+template <int P = LD_DEF>
 __device__ __forceinline__ void flat_dma(const float* __restrict__ src, int n, float* dst, int wave, int lane) {
     for (int i = wave; i < (n >> 8); i += NWB)
-        __builtin_amdgcn_global_load_lds((gvoid_t*)(src + 256 * i + 4 * lane), (lvoid_t*)(dst + 256 * i), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gvoid_t*)(src + 256 * i + 4 * lane), (lvoid_t*)(dst + 256 * i), 16, 0,
+                                         ld_dma_aux<P>());
 }
 
 // workgroup barrier for LDS hand-offs only: unlike __syncthreads() it does not drain the wave's
@@ -279,7 +299,7 @@ __device__ __forceinline__ void pass_a_body(const Geo& g, const float* __restric
     // compile-time shapes: the first trial's x goes out by LDS-DMA before anything else; the pad fill,
     // the weight loads and the edge decode below overlap it, and one barrier waits for all of it
     if constexpr (XDMA) {
-        if (b0 < b1) x_dma_asm(x + fold_row(perm, row0, b0) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
+        if (b0 < b1) x_dma_asm<x_pol<FOLD>()>(x + fold_row(perm, row0, b0) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
         zero_pads(sm, NXB * C + F2, RS, LP, T, tid);
     } else {
         zero_fill<false>(sm, (C + F2) * RS, C, RS, LP, T, tid);
@@ -362,7 +382,7 @@ __device__ __forceinline__ void pass_a_body(const Geo& g, const float* __restric
     if constexpr (XDMA) {
         barrier_vm<0>();                              // the first x landed, pads and tables written
     } else {
-        if (b0 < b1) x_prefetch<PF, NTB>(x + fold_row(perm, row0, b0) * (C * XP), C, T, pf, tid);
+        if (b0 < b1) x_prefetch<PF, NTB, x_pol<FOLD>()>(x + fold_row(perm, row0, b0) * (C * XP), C, T, pf, tid);
         __syncthreads();
         x_store<PF, NTB>(pf, C, T, RS, LP, Xb, tid);
         __syncthreads();
@@ -387,7 +407,7 @@ __device__ __forceinline__ void pass_a_body(const Geo& g, const float* __restric
             }
             if (bn < b1) {
                 if (EEGNET_LDSX_A != 7)
-                    x_dma_asm(x + fold_row(perm, row0, bn) * (C * XP), C, T, XP, RS, LP,
+                    x_dma_asm<x_pol<FOLD>()>(x + fold_row(perm, row0, bn) * (C * XP), C, T, XP, RS, LP,
                               sm + ((bn - b0) & 1) * C * RS, wave, lane);
                 xstat_dma(bn, (bn - b0) & 1);
             }
@@ -493,7 +513,7 @@ __device__ __forceinline__ void pass_a_body(const Geo& g, const float* __restric
         barrier_lds();                                     // Ss complete, x read for good (LDS only:
                                                            // the previous trial's v stores stay in flight)
         if constexpr (!XDMA)
-            if (bn < b1) x_prefetch<PF, NTB>(x + fold_row(perm, row0, bn) * (C * XP), C, T, pf, tid);   // live over the FIR only
+            if (bn < b1) x_prefetch<PF, NTB, x_pol<FOLD>()>(x + fold_row(perm, row0, bn) * (C * XP), C, T, pf, tid);   // live over the FIR only
         TRACE_PH(g, 0, 1, tph_);
         // s rows -> the s plane [B][F2][T] (pass E's lag-correlation operand)
         if (EEGNET_LDSX_A != 5) s_rows_store<NTB>(Ss, sg + (size_t)b * F2 * s_pitch(T), F2, T, RS, LP, tid);
@@ -1190,7 +1210,7 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
     if constexpr (!DMA) {
         if (b0 < b1) {
             s_rows_put();
-            x_prefetch<PF, NTB>(x + fold_row(perm, row0, b0) * (C * XP), C, T, pfx, tid);
+            x_prefetch<PF, NTB, x_pol<FOLD>()>(x + fold_row(perm, row0, b0) * (C * XP), C, T, pfx, tid);
             x_store<PF, NTB>(pfx, C, T, RS, LP, Xb, tid);
         }
         __syncthreads();
@@ -1268,7 +1288,7 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
             // x DMA: this trial's x rows for the dws GEMM (the buffer was last read by the previous
             // trial's GEMM); they land during the lag correlation / FIR^T, by the next barrier
             if (EEGNET_LDSX_E != 7)
-                x_dma_asm(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
+                x_dma_asm<x_pol<FOLD>()>(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
             TRACE_PH(g, 4, 2, tph_);
             {
                 float tl[K1];
@@ -1418,7 +1438,7 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
             // x DMA: this trial's x rows for the dws GEMM (the buffer was last read by the previous
             // trial's GEMM); they land during the lag correlation / FIR^T, by the next barrier
             if (EEGNET_LDSX_E != 7)
-                x_dma_asm(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
+                x_dma_asm<x_pol<FOLD>()>(x + fold_row(perm, row0, b) * (C * XP), C, T, XP, RS, LP, Xb, wave, lane);
             TRACE_PH(g, 4, 2, tph_);
             {
                 float tl[K1];
@@ -1614,7 +1634,7 @@ __device__ __forceinline__ void pass_e_body(const Geo& g, const float* prm,   //
             TRACE_PH(g, 4, 4, tph_);
             if (bn < b1) {                                     // next s / x loads: registers over the GEMM only
                 s_rows_load(bn);
-                x_prefetch<PF, NTB>(x + fold_row(perm, row0, bn) * (C * XP), C, T, pfx, tid);
+                x_prefetch<PF, NTB, x_pol<FOLD>()>(x + fold_row(perm, row0, bn) * (C * XP), C, T, pfx, tid);
                 asm volatile("" ::: "memory");                 // they issue here, ahead of the GEMM
             }
             TRACE_PH(g, 4, 5, tph_);
