@@ -108,6 +108,14 @@ _SIGS = {
     "eegnet_fir_chunk": (ctypes.c_int, []),
     "eegnet_fir": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,
                                   ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),
+    "eegnet_resample_max_taps": (ctypes.c_int, []),
+    "eegnet_resample_max_up": (ctypes.c_int, []),
+    "eegnet_resample_chunk": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "eegnet_resample_count": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "eegnet_resample": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int64,
+                                       ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),
     "eegnet_ems_chunk": (ctypes.c_int, []),
     "eegnet_ems_scratch_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
     "eegnet_ems": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,

@@ -273,6 +273,8 @@ static void ensure_attrs() {
     set_attrs_shape<64, 0, 0, 0>();
     hipFuncSetAttribute((const void*)k_xstats<32>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     hipFuncSetAttribute((const void*)k_xstats<64>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    hipFuncSetAttribute((const void*)k_resample<float>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    hipFuncSetAttribute((const void*)k_resample<double>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     set_attrs_shapes(NarrowShapes{});
     g_attr_done = true;
 }
@@ -1008,6 +1010,92 @@ static bool bytes_overlap(const void* a, double na, const void* b, double nb) {
     return a && b && na > 0 && nb > 0 && a0 < b0 + nb && b0 < a0 + na;
 }
 
+// The integers of an eegnet_resample call: the reduced ratio, the filter's geometry, the call's first output
+// and its count.  Everything eegnet_resample_count answers, so nothing here looks at a pointer.
+//   done(t)   outputs whose whole support lies in the first t samples: m down + half < t up
+//   all(t)    outputs of a recording of t samples: ceil(t up / down)
+static int rs_plan(int64_t n_samples, int64_t n_before, int n_taps, int up, int down, int mode, RsCall* rc) {
+    if (mode < EEGNET_RESAMPLE_WHOLE || mode > EEGNET_RESAMPLE_TAIL)
+        return fail(EEGNET_EINVAL, "eegnet_resample: unknown mode %d", mode);
+    if (n_taps < 1 || n_taps > RS_MAX_TAPS || (n_taps & 1) == 0)
+        return fail(EEGNET_EINVAL, "eegnet_resample: n_taps must be odd and in [1, %d] (got %d)", RS_MAX_TAPS, n_taps);
+    if (up < 1 || down < 1)
+        return fail(EEGNET_EINVAL, "eegnet_resample: up and down must be >= 1 (got %d/%d)", up, down);
+    int a = up, b = down;
+    while (b) { const int t = a % b; a = b; b = t; }
+    const int u = up / a, d = down / a;
+    if (u == d) return fail(EEGNET_EINVAL, "eegnet_resample: %d/%d reduces to 1/1: nothing to resample", up, down);
+    if (u > RS_MAX_UP || d > RS_MAX_DOWN)
+        return fail(EEGNET_EINVAL, "eegnet_resample: %d/%d reduces to %d/%d, beyond up <= %d, down <= %d", up, down, u,
+                    d, RS_MAX_UP, RS_MAX_DOWN);
+    const int half = (n_taps - 1) / 2, Q = half / u;
+    const int64_t n_cap = ((int64_t)1 << 61) / std::max(u, d);
+    if (n_before < 0 || n_before > n_cap)
+        return fail(EEGNET_EINVAL, "eegnet_resample: n_before must be in [0, %lld] (got %lld)", (long long)n_cap,
+                    (long long)n_before);
+    const bool opens = mode == EEGNET_RESAMPLE_WHOLE || mode == EEGNET_RESAMPLE_FIRST;
+    if (opens && n_before != 0)
+        return fail(EEGNET_EINVAL, "eegnet_resample: a recording's first samples come after none (n_before = %lld)",
+                    (long long)n_before);
+    if (!opens && n_before < Q + 2)
+        return fail(EEGNET_EINVAL, "eegnet_resample: a stream's first block holds at least %d samples (n_before = %lld)",
+                    Q + 2, (long long)n_before);
+    const int64_t n_min = mode == EEGNET_RESAMPLE_FIRST ? Q + 2 : 1;
+    if (mode == EEGNET_RESAMPLE_TAIL) {
+        if (n_samples != 0)
+            return fail(EEGNET_EINVAL, "eegnet_resample: the tail call takes no samples (n_samples = %lld)",
+                        (long long)n_samples);
+    } else if (n_samples < n_min || n_samples > n_cap - n_before) {
+        return fail(EEGNET_EINVAL, "eegnet_resample: n_samples must be in [%lld, %lld]%s (got %lld)", (long long)n_min,
+                    (long long)(n_cap - n_before), mode == EEGNET_RESAMPLE_FIRST ? ", at least half / up + 2 for a "
+                    "stream's first block" : "", (long long)n_samples);
+    }
+    const auto done = [&](int64_t t) { const int64_t v = t * u - half - 1; return v >= 0 ? v / d + 1 : (int64_t)0; };
+    const auto all = [&](int64_t t) { return (t * u + d - 1) / d; };
+    const int64_t end = n_before + n_samples;
+    rc->n = n_samples;
+    rc->t0 = n_before;
+    rc->m_lo = opens ? 0 : done(n_before);
+    rc->n_out = (mode == EEGNET_RESAMPLE_WHOLE || mode == EEGNET_RESAMPLE_TAIL ? all(end) : done(end)) - rc->m_lo;
+    rc->L = n_taps;
+    rc->half = half;
+    rc->up = u;
+    rc->down = d;
+    rc->K = (n_taps + u - 1) / u;
+    rc->H = 2 * Q + 2;
+    rc->head_ext = opens;
+    rc->tail_ext = mode == EEGNET_RESAMPLE_WHOLE || mode == EEGNET_RESAMPLE_TAIL;
+    // a stream's recording holds at least Q + 2 samples (its first block does): both ends reflect Q + 1
+    rc->refl = mode == EEGNET_RESAMPLE_WHOLE ? std::min<int64_t>(Q + 1, n_samples - 1) : Q + 1;
+    rc->share = RS_NT % u == 0;
+    // the chunk: the most outputs, up to RS_CH, whose span fits beside the table; whole workgroups' worth when
+    // there is room for that.  The outputs do not depend on it.
+    const long long room = LDS_MAX / 8 - (long long)rc->K * u - 1 - rc->K;
+    if (room < 0)
+        return fail(EEGNET_EINVAL, "eegnet_resample: %d taps at up = %d do not fit the LDS beside one output's span",
+                    n_taps, u);
+    long long ch = std::min<long long>(RS_CH, ((room + 1) * u - 1) / d + 1);
+    if (ch >= RS_NT) ch -= ch % RS_NT;
+    rc->ch = (int)ch;
+    rc->n_chunks = rc->n_out > 0 ? (rc->n_out - 1) / ch + 1 : 0;
+    return 0;
+}
+
+// the two launches of eegnet_resample on rows of T: the outputs (when there are any), then the next history
+template <class T>
+static int rs_launch(const RsCall& rc, const void* x, const double* taps, const double* hist_in, double* hist_out,
+                     float* y, hipStream_t s) {
+    if (rc.n_out > 0) {
+        const size_t lds = ((size_t)rc.K * rc.up + (size_t)rs_span_doubles(rc.ch, rc.up, rc.down, rc.K)) * sizeof(double);
+        if (int r = launch(KID_NONE, "k_resample", k_resample<T>, dim3((unsigned)(rc.n_rows * rc.n_groups)), dim3(RS_NT),
+                           lds, s, rc, (const T*)x, taps, hist_in, y)) return r;
+    }
+    const long long nh = rc.n_rows * (long long)rc.H;
+    if (!hist_out) return 0;
+    return launch(KID_NONE, "k_resample_hist", k_resample_hist<T>, dim3((unsigned)((nh + RS_NT - 1) / RS_NT)), dim3(RS_NT),
+                  0, s, rc, (const T*)x, hist_in, hist_out);
+}
+
 extern "C" {
 
 int eegnet_train_step_folds(const eegnet_dims* dims, int nfolds, const eegnet_fold* folds, int64_t row0,
@@ -1257,6 +1345,79 @@ int eegnet_fir(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, i
     hipStream_t s = (hipStream_t)stream;
     return x_is_f64 ? fir_launch<double>(fc, x, taps, hist_in, hist_out, y, s)
                     : fir_launch<float>(fc, x, taps, hist_in, hist_out, y, s);
+}
+
+int eegnet_resample_max_taps(void) { return RS_MAX_TAPS; }
+
+int eegnet_resample_max_up(void) { return RS_MAX_UP; }
+
+int eegnet_resample_chunk(int n_taps, int up, int down) {
+    RsCall rc;
+    if (int r = rs_plan(1, 0, n_taps, up, down, EEGNET_RESAMPLE_WHOLE, &rc)) return r;
+    return rc.ch;
+}
+
+int eegnet_resample_count(int64_t n_samples, int64_t n_before, int n_taps, int up, int down, int mode, int64_t* n_out) {
+    if (int r = check_ptrs(n_out, "n_out")) return r;
+    RsCall rc;
+    if (int r = rs_plan(n_samples, n_before, n_taps, up, down, mode, &rc)) return r;
+    *n_out = rc.n_out;
+    return 0;
+}
+
+int eegnet_resample(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, int64_t x_pitch, const double* taps,
+                    int n_taps, int up, int down, int ends, float* y, int64_t y_pitch, int64_t n_before,
+                    const double* hist_in, double* hist_out, int mode, void* stream) {
+    RsCall rc;
+    if (int r = rs_plan(n_samples, n_before, n_taps, up, down, mode, &rc)) return r;
+    if (mode != EEGNET_RESAMPLE_TAIL)
+        if (int r = check_ptrs(x, "x")) return r;
+    if (int r = check_ptrs(taps, "taps")) return r;
+    if (rc.n_out > 0)                                   // (a continuation too short for an output writes none)
+        if (int r = check_ptrs(y, "y")) return r;
+    if (ends != EEGNET_RESAMPLE_ENDS_ZERO && ends != EEGNET_RESAMPLE_ENDS_REFLECT)
+        return fail(EEGNET_EINVAL, "eegnet_resample: unknown ends %d", ends);
+    if (n_rows < 1) return fail(EEGNET_EINVAL, "eegnet_resample: n_rows must be >= 1 (got %lld)", (long long)n_rows);
+    const bool need_in = mode == EEGNET_RESAMPLE_NEXT || mode == EEGNET_RESAMPLE_TAIL;
+    const bool need_out = mode == EEGNET_RESAMPLE_FIRST || mode == EEGNET_RESAMPLE_NEXT;
+    if (need_in && !hist_in) return fail(EEGNET_EINVAL, "eegnet_resample: this mode reads the history: hist_in is NULL");
+    if (need_out && !hist_out) return fail(EEGNET_EINVAL, "eegnet_resample: this mode writes the history: hist_out is NULL");
+    rc.n_rows = n_rows;
+    rc.reflect = ends == EEGNET_RESAMPLE_ENDS_REFLECT;
+    if (rc.n_chunks > FIR_MAX_GRID / n_rows || (int64_t)rc.H > FIR_MAX_GRID / n_rows * RS_NT)
+        return fail(EEGNET_EINVAL, "eegnet_resample: n_rows = %lld rows of %lld chunks (%d outputs each) exceed the grid "
+                    "limit of %lld workgroups", (long long)n_rows, (long long)rc.n_chunks, rc.ch, (long long)FIR_MAX_GRID);
+    // a workgroup stages the table once and runs up to RS_CPW chunks under it, while that leaves the chip
+    // RS_MIN_GRID workgroups to spread
+    rc.cpw = (int)std::max<int64_t>(1, std::min<int64_t>(RS_CPW, n_rows * rc.n_chunks / RS_MIN_GRID));
+    rc.n_groups = (rc.n_chunks + rc.cpw - 1) / rc.cpw;
+    if (mode != EEGNET_RESAMPLE_TAIL && x_pitch < n_samples)
+        return fail(EEGNET_EINVAL, "eegnet_resample: x_pitch = %lld is below n_samples = %lld", (long long)x_pitch,
+                    (long long)n_samples);
+    if (y_pitch < rc.n_out)
+        return fail(EEGNET_EINVAL, "eegnet_resample: y_pitch = %lld is below the %lld outputs of a row", (long long)y_pitch,
+                    (long long)rc.n_out);
+    rc.x_pitch = x_pitch;
+    rc.y_pitch = y_pitch;
+    const uintptr_t xa = x_is_f64 ? 7 : 3;
+    if (((uintptr_t)x & xa) || ((uintptr_t)y & 3) || ((uintptr_t)taps & 7) || ((uintptr_t)hist_in & 7) ||
+        ((uintptr_t)hist_out & 7))
+        return fail(EEGNET_EINVAL, "eegnet_resample: x, y, taps and the histories must be aligned to their element size");
+    // a workgroup's outputs would overwrite inputs its neighbours still read: no resampling in place
+    const double xb = ((double)(n_rows - 1) * (double)x_pitch + (double)n_samples) * (x_is_f64 ? 8.0 : 4.0);
+    const double yb = ((double)(n_rows - 1) * (double)y_pitch + (double)rc.n_out) * 4.0;
+    const double hb = (double)n_rows * (double)rc.H * 8.0;
+    if (mode != EEGNET_RESAMPLE_TAIL && bytes_overlap(x, xb, y, yb))
+        return fail(EEGNET_EINVAL, "eegnet_resample: y overlaps x (resampling in place is not supported)");
+    if (need_in && need_out && bytes_overlap(hist_in, hb, hist_out, hb))
+        return fail(EEGNET_EINVAL, "eegnet_resample: hist_out overlaps hist_in (the call reads one and writes the other)");
+    if (!need_in) hist_in = nullptr;
+    if (!need_out) hist_out = nullptr;
+    if (rc.n_out == 0 && !hist_out) return 0;
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    return x_is_f64 ? rs_launch<double>(rc, x, taps, hist_in, hist_out, y, s)
+                    : rs_launch<float>(rc, x, taps, hist_in, hist_out, y, s);
 }
 
 // chunks per row and workgroups of an eegnet_ems call; the sizes are checked before anything is multiplied

@@ -48,5 +48,6 @@
 #include "eegnet_infer_bf16c.hip"
 #include "eegnet_ems.hip"
 #include "eegnet_fir.hip"
+#include "eegnet_resample.hip"
 #include "eegnet_geometry.h"
 #include "eegnet_host.hip"

@@ -7,6 +7,7 @@ Every function here runs the HIP kernels of ``csrc/eegnet_kernels.hip`` through
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 
 import torch
@@ -345,6 +346,104 @@ def fir(x, taps, out=None, *, mode=FIR_WHOLE, hist_in=None, hist_out=None, lead=
         _ptr(x), ctypes.c_int(is64), ctypes.c_int64(R * C), ctypes.c_int64(N), ctypes.c_int64(xp), _ptr(taps),
         ctypes.c_int(L), _ptr(out), ctypes.c_int64(op), _ptr(hist_in), _ptr(hist_out), ctypes.c_int(mode), _stream()),
         "eegnet_fir")
+    return out
+
+
+RESAMPLE_WHOLE, RESAMPLE_FIRST, RESAMPLE_NEXT, RESAMPLE_TAIL = 0, 1, 2, 3    # include/eegnet_abi.h EEGNET_RESAMPLE_*
+RESAMPLE_ENDS = {"zero": 0, "reflect_limited": 1}                             # EEGNET_RESAMPLE_ENDS_*
+
+
+def resample_max_taps() -> int:
+    """eegnet_resample_max_taps: the longest prototype filter eegnet_resample takes.  Host-side only."""
+    return int(_lib.load().eegnet_resample_max_taps())
+
+
+def resample_max_up() -> int:
+    """eegnet_resample_max_up: the largest reduced ``up`` eegnet_resample takes.  Host-side only."""
+    return int(_lib.load().eegnet_resample_max_up())
+
+
+def resample_chunk(n_taps: int, up: int, down: int) -> int:
+    """eegnet_resample_chunk: the outputs of one workgroup of the resampling kernel for this prototype and ratio
+    (sized to the LDS; the outputs' bits do not depend on it).  Host-side only."""
+    ch = int(_lib.load().eegnet_resample_chunk(ctypes.c_int(n_taps), ctypes.c_int(up), ctypes.c_int(down)))
+    if ch < 0:
+        _lib.check(ch, "eegnet_resample_chunk")
+    return ch
+
+
+def resample_count(n_samples: int, n_taps: int, up: int, down: int, *, mode=RESAMPLE_WHOLE, n_before=0) -> int:
+    """eegnet_resample_count: the outputs per row that a call with these integers writes.  Host-side only."""
+    out = ctypes.c_int64(0)
+    _lib.check(_lib.load().eegnet_resample_count(ctypes.c_int64(n_samples), ctypes.c_int64(n_before), ctypes.c_int(n_taps),
+                                                 ctypes.c_int(up), ctypes.c_int(down), ctypes.c_int(mode),
+                                                 ctypes.byref(out)), "eegnet_resample_count")
+    return int(out.value)
+
+
+def resample(x, taps, up, down, out=None, *, ends="reflect_limited", mode=RESAMPLE_WHOLE, n_before=0, hist_in=None,
+             hist_out=None, lead=None):
+    """Rational polyphase resampling of continuous recordings (eegnet_resample; scipy's ``resample_poly``, not the
+    FFT method the reference's ``raw.resample`` defaults to): per row, with c = m down + half,
+    y[m] = sum_n taps[c - n up] u[n], in float64 on the device, rounded to float32 once.  ``x`` is [R, C, N]
+    float32 or float64 on the device and is read in place when its rows lie at one pitch; anything else is made
+    contiguous first.  ``taps``: a contiguous float64 [L] device tensor, L odd.  ``ends``: "zero" or
+    "reflect_limited".  ``mode``: RESAMPLE_WHOLE; RESAMPLE_FIRST, a stream's first block (``hist_out`` written);
+    RESAMPLE_NEXT, a continuation after ``n_before`` samples (``hist_in`` read, ``hist_out`` written);
+    RESAMPLE_TAIL, the stream's last outputs from ``hist_in`` after ``n_before`` samples (``x`` is None and
+    ``lead`` = (R, C)).  The histories are contiguous float64 [R * C, 2 (L // 2 // up) + 2] device tensors (``up``
+    reduced), two different ones.  The output count is ``resample_count`` of the same integers.  ``out``: a
+    float32 [R, C, outputs] device tensor whose rows lie at one pitch and that does not overlap ``x``
+    (ValueError), else a new contiguous one."""
+    require_device(taps, "taps")
+    if taps.dtype != torch.float64 or taps.dim() != 1 or not taps.is_contiguous():
+        raise ValueError("taps must be a contiguous float64 [L] tensor on the device")
+    if ends not in RESAMPLE_ENDS:
+        raise ValueError(f"ends must be one of {sorted(RESAMPLE_ENDS)} (got {ends!r})")
+    L, up, down = int(taps.shape[0]), int(up), int(down)
+    if mode == RESAMPLE_TAIL:
+        if x is not None or lead is None:
+            raise ValueError("the tail call takes no samples: x is None and lead = (R, C)")
+        R, C = (int(v) for v in lead)
+        N, xp, is64, dev = 0, 0, False, taps.device
+    else:
+        require_device(x, "x")
+        if x.dtype not in (torch.float32, torch.float64):
+            raise RuntimeError(f"resample expects float32 or float64 input (got {x.dtype})")
+        if x.dim() != 3:
+            raise RuntimeError(f"expected recordings [R, C, N], got {list(x.shape)}")
+        R, C, N = x.shape
+        xp = _row_pitch(x)
+        if xp is None:
+            x, xp = x.contiguous(), N
+        is64, dev = x.dtype == torch.float64, x.device
+    if R * C == 0 or (N == 0 and mode != RESAMPLE_TAIL):
+        raise ValueError(f"an empty recording cannot be resampled (got {[R, C, N]})")
+    n_out = resample_count(N, L, up, down, mode=mode, n_before=n_before)
+    if out is None:
+        out = torch.empty((R, C, n_out), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (R, C, n_out) or out.dtype != torch.float32 or out.device != dev or _row_pitch(out) is None:
+        raise ValueError(f"out must be a float32 {[R, C, n_out]} tensor on {dev} whose rows lie at one pitch "
+                         f"(last stride 1)")
+    g = math.gcd(up, down)
+    H = 2 * ((L // 2) // (up // g)) + 2
+    for name, h in (("hist_in", hist_in), ("hist_out", hist_out)):
+        if h is not None and (h.dtype != torch.float64 or tuple(h.shape) != (R * C, H) or not h.is_contiguous()
+                              or h.device != dev):
+            raise ValueError(f"{name} must be a contiguous float64 [{R * C}, {H}] tensor on {dev}")
+    op = _row_pitch(out)
+    if mode != RESAMPLE_TAIL and n_out > 0:
+        # the library rejects it too (EEGNET_EINVAL): said here as the ValueError the Python surface promises
+        x0, x1 = x.data_ptr(), x.data_ptr() + ((R * C - 1) * xp + N) * x.element_size()
+        y0, y1 = out.data_ptr(), out.data_ptr() + ((R * C - 1) * op + n_out) * 4
+        if x0 < y1 and y0 < x1:
+            raise ValueError("out overlaps x: resampling in place is not supported (a workgroup's outputs would "
+                             "overwrite inputs its neighbours still read)")
+    _lib.check(_lib.load().eegnet_resample(
+        _ptr(x), ctypes.c_int(is64), ctypes.c_int64(R * C), ctypes.c_int64(N), ctypes.c_int64(xp), _ptr(taps),
+        ctypes.c_int(L), ctypes.c_int(up), ctypes.c_int(down), ctypes.c_int(RESAMPLE_ENDS[ends]), _ptr(out),
+        ctypes.c_int64(op), ctypes.c_int64(n_before), _ptr(hist_in), _ptr(hist_out), ctypes.c_int(mode), _stream()),
+        "eegnet_resample")
     return out
 
 

@@ -13,6 +13,8 @@
  *   raw_exponential_moving_standardize  src/eegnet_repl/dataset.py:45-70 -> eegnet_ems
  *   raw.filter(4., 38., fir_design='firwin')  src/eegnet_repl/dataset.py:113-125 -> eegnet_fir
  *   mne.Epochs(tmin=0.5, tmax=2.5) + model.eval()  src/eegnet_repl/dataset.py:223-224 -> eegnet_forward_eval_windows_at
+ *   raw.resample(128, npad="auto")  src/eegnet_repl/dataset.py:114 -> eegnet_resample (the polyphase method, not
+ *                                                                       the FFT method that call defaults to)
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer (hipMalloc / torch CUDA tensor) unless noted.  The library never
@@ -411,6 +413,56 @@ int eegnet_fir_chunk(void);
 int eegnet_fir(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, int64_t x_pitch,
                const double* taps, int n_taps, float* y, int64_t y_pitch, const double* hist_in,
                double* hist_out, int mode, void* stream);
+
+/* Rational polyphase resampling up/down of continuous recordings: scipy.signal.resample_poly, mne's
+ * method="polyphase".  This is NOT the method the reference's raw.resample(128, npad="auto") defaults to (mne's
+ * FFT method, a DFT of the whole padded recording, which cannot stream); the two differ at the recording's
+ * ends and by the anti-alias filter's response (DESIGN.md 4.8 has the measured difference after the band-pass).
+ * up/down is reduced by its gcd first (128/250 -> 64/125).  Per row of N samples, with the prototype taps
+ * h[0..L-1] (fp64, on the device; L = n_taps = 2 half + 1), Q = half / up and c = m down + half, output m of the
+ * ceil(N up / down) is
+ *     y[m] = sum_{n = ceil((c - 2 half) / up) .. floor(c / up)} h[c - n up] u[n]
+ * added in the order of ascending tap index c - n up by one fp64 fused multiply-add per term from a zero start
+ * (at most ceil(L / up) terms) and rounded to fp32 once.  u is the row extended past its ends by `ends`:
+ *   EEGNET_RESAMPLE_ENDS_ZERO     u = 0 outside [0, N): resample_poly's default padtype='constant'
+ *   EEGNET_RESAMPLE_ENDS_REFLECT  the band-pass's odd reflection: u[-j] = 2 x[0] - x[j], u[N-1+j] = 2 x[N-1] - x[N-1-j]
+ *                                 for 1 <= j <= min(Q + 1, N - 1), zero beyond (no output reaches further)
+ * An output's value is a function of the taps and of the values of u in its support alone: not of the chunking,
+ * of n_rows, of a pitch or an alignment, nor of the mode that produced it.  n_before is the number of samples of
+ * the recording consumed before this block; it alone decides which outputs m of the recording the call emits,
+ * and their phases come from m.  With done(t) = the outputs m with m down + half < t up (whole support within
+ * the first t samples):
+ *   EEGNET_RESAMPLE_WHOLE  whole rows: n_samples >= 1 in, ceil(n_samples up / down) out; n_before = 0.
+ *   EEGNET_RESAMPLE_FIRST  a stream's first block: n_samples >= Q + 2 in (the head's reflection is the block's
+ *                          own), outputs 0 .. done(n_samples) - 1 out; n_before = 0; hist_out receives the
+ *                          last 2 Q + 2 values of u as fp64 [n_rows][2 Q + 2].
+ *   EEGNET_RESAMPLE_NEXT   a continuation: n_samples >= 1 in, outputs done(n_before) .. done(n_before +
+ *                          n_samples) - 1 out (none, for a short block, is a valid count); the left context is
+ *                          hist_in, hist_out receives the last 2 Q + 2 values of history + block; hist_out must
+ *                          not be hist_in (the caller ping-pongs two buffers).
+ *   EEGNET_RESAMPLE_TAIL   the stream's end: n_samples = 0 (x is not read and may be NULL), n_before = N, outputs
+ *                          done(N) .. ceil(N up / down) - 1 out, the right end extended from hist_in.
+ * The outputs of FIRST, NEXT.. and TAIL laid end to end are the WHOLE call's on the concatenated blocks, bit for
+ * bit.  eegnet_resample_count returns in *n_out the outputs per row a call with these integers writes (host only;
+ * it validates them as eegnet_resample does).  x, y, the pitches, the alignment and the overlap rule are
+ * eegnet_fir's: x fp32 or fp64 at any element alignment, y fp32, x_pitch >= n_samples, y_pitch >= the outputs of a
+ * row, no byte outside a row's valid samples read, none outside its outputs written, and a y that overlaps x
+ * rejected.  n_taps is odd and <= eegnet_resample_max_taps() (4097); the reduced up is <= eegnet_resample_max_up()
+ * (256), the reduced down <= 2^20, up != down; (n_before + n_samples) max(up, down) <= 2^61.  One workgroup per
+ * row and chunk of outputs, the chunk sized by the host to the LDS; n_rows * chunks <= 2^31 - 1.  One launch for
+ * the outputs and one for the history, on `stream`; no atomics, no allocation, no host synchronisation:
+ * capturable in a hipGraph.  The validation needs no GPU. */
+enum { EEGNET_RESAMPLE_WHOLE = 0, EEGNET_RESAMPLE_FIRST = 1, EEGNET_RESAMPLE_NEXT = 2, EEGNET_RESAMPLE_TAIL = 3 };
+enum { EEGNET_RESAMPLE_ENDS_ZERO = 0, EEGNET_RESAMPLE_ENDS_REFLECT = 1 };
+int eegnet_resample_max_taps(void);
+int eegnet_resample_max_up(void);
+/* the outputs of one workgroup of a call with this prototype and ratio (> 0), or a negative EEGNET_E* (host only) */
+int eegnet_resample_chunk(int n_taps, int up, int down);
+int eegnet_resample_count(int64_t n_samples, int64_t n_before, int n_taps, int up, int down, int mode,
+                          int64_t* n_out);
+int eegnet_resample(const void* x, int x_is_f64, int64_t n_rows, int64_t n_samples, int64_t x_pitch,
+                    const double* taps, int n_taps, int up, int down, int ends, float* y, int64_t y_pitch,
+                    int64_t n_before, const double* hist_in, double* hist_out, int mode, void* stream);
 
 /* Exponential moving standardisation of continuous recordings: the reference's
  * raw_exponential_moving_standardize (dataset.py:45-70), the step in front of eegnet_forward_eval_windows.
