@@ -104,6 +104,11 @@ _SIGS = {
     "eegnet_forward_eval_windows_at": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int64,
                                                       ctypes.c_int64, ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp,
                                                       _vp]),
+    "eegnet_frozen_step_windows": (ctypes.c_int, [ctypes.POINTER(Dims), _vp, _vp, _vp, ctypes.c_int64,
+                                                  ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64,
+                                                  _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
+                                                  _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                  ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int]),
     "eegnet_fir_max_taps": (ctypes.c_int, []),
     "eegnet_fir_chunk": (ctypes.c_int, []),
     "eegnet_fir": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,

@@ -1,7 +1,9 @@
 // eegnet_frozen.hip -- frozen-BatchNorm fine-tuning: the fused forward + loss + backward + parameter
 // gradient kernel behind eegnet_frozen_step / eegnet_forward_frozen, and the reduction of its
 // per-workgroup partial rows; their fold-indexed instantiations (FOLD: blockIdx.y is the model) and the
-// fold-indexed Adam behind eegnet_frozen_step_folds.  Included by eegnet_kernels.hip (one translation unit).
+// fold-indexed Adam behind eegnet_frozen_step_folds; and the instantiations that read their batch as windows of
+// continuous recordings in place (FzWin, behind eegnet_frozen_step_windows: eegnet_windows.hip's table loader).
+// Included by eegnet_kernels.hip (one translation unit).
 //
 // With the BatchNorm layers frozen (running statistics used and left untouched, dropout still on)
 // every trial is independent: none of the five batch-global reductions that split the train step into
@@ -98,6 +100,39 @@ __device__ __forceinline__ float fz_b2_add(float acc, float a, float e) {
 template <bool FOLD> struct FzFold {};
 template <> struct FzFold<true> { FoldCall fc; };
 
+// The loader policy of k_frozen, its last template parameter and the type of its last argument.  FzFold<FOLD>
+// (the default) takes batch row b from x as a contiguous [C][T] trial: xrow / x_prefetch / trial_x_first.
+// FzWin (eegnet_frozen_step_windows) takes it from a table of windows of continuous recordings, read where
+// they lie: batch row b is table entry e = sel ? clamp(sel[b], 0, ac.total - 1) : b, its x the window
+// win_org(ac, C, T, e) places (start and recording clamped into the recordings, load width per window) and
+// its label lab[e]; dlogits, logits, the injected masks and the dropout counters stay indexed by b.
+// win_prefetch fills the registers x_prefetch would fill from the window copied out, so everything behind
+// the loader carries the bits of the default policy on the copy.
+struct FzWin {
+    WinAtCall ac;                 // total: the table's length
+    const long long* sel;         // [B] table entries of the batch, device, nullable (entry b)
+};
+template <class Src> constexpr bool fz_is_win = false;
+template <> constexpr bool fz_is_win<FzWin> = true;
+
+// table entry of batch row b (wave-uniform)
+__device__ __forceinline__ int fz_entry(const FzWin& fw, int b) {
+    if (!fw.sel) return b;
+    long long e = fw.sel[b];
+    e = e < 0 ? 0 : e >= fw.ac.total ? fw.ac.total - 1 : e;
+    return (int)e;
+}
+
+// the windowed loader's x_prefetch: batch row b's window, at its clamped origin and load width.  (A function
+// that takes C, T and tid by value, not a by-reference lambda in the kernel: with the lambda every
+// compile-time-shape kernel that calls x_store -- the pre-existing ones included -- came out 8 to 36 bytes
+// longer, its x_store index arithmetic no longer folded)
+template <int PF>
+__device__ __forceinline__ void fz_win_prefetch(const FzWin& fw, int C, int T, int b, float (&pf)[PF], int tid) {
+    const WinOrg org = win_org(fw.ac, C, T, fz_entry(fw, b));
+    win_prefetch<PF>(org.row0, fw.ac.pitch, org.vec, C, T, pf, tid);
+}
+
 // STAGE (EEGNET_TRAIN_*): the first trainable module in network order.  The flat parameter buffer is in
 // network order, so the trainable set is the suffix [o_g2 | o_w2 | o_Wfc, nparam) of it, and the backward of
 // a trial stops as soon as the last sum of that suffix is complete:
@@ -119,13 +154,15 @@ template <> struct FzFold<true> { FoldCall fc; };
 //                                                  also what keeps Hs / Lg / Qs / D2s of this trial from the
 //                                                  next one's writers
 constexpr int FZ_ALL = 0, FZ_AGG = 1, FZ_B2 = 2, FZ_CLS = 3;
-template <int K1, int CC, int TT, int FF, bool BWD, bool FOLD = false, int STAGE = FZ_ALL>
+template <int K1, int CC, int TT, int FF, bool BWD, bool FOLD = false, int STAGE = FZ_ALL, class Src = FzFold<FOLD>>
 __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__ prm,
                                                 const float* __restrict__ bn, const float* __restrict__ x,
                                                 const float* __restrict__ dlog, const int64_t* __restrict__ lab,
                                                 const uint8_t* __restrict__ m2, const uint8_t* __restrict__ m3,
-                                                float* __restrict__ logits, float* part, FzFold<FOLD> fold) {
+                                                float* __restrict__ logits, float* part, Src fold) {
     using G_ = KG<K1>;
+    constexpr bool WIN = fz_is_win<Src>;                // x and the labels through a table of windows (x unused)
+    static_assert(!(WIN && FOLD), "the windowed loader serves the single-model step");
     EEG_DIMS(g);
     // fold launch: the batch is rows perm[row0 ...] (or row0 ...) of the fold's x / labels, seeded by the
     // mean cross-entropy, its dropout key mix(seed, koff + *step) as a KEY_FROM_STEP single call's
@@ -206,12 +243,24 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
     float pf[PF];
     // (xrow is evaluated before the guard, a perm[] load included: the host launches min(B, CUs) workgroups,
     // so blockIdx.x < g.B in every launch and the guard only mirrors the other kernels')
-    trial_x_first<PF>((int)blockIdx.x < g.B, xrow(blockIdx.x), C, T, RS, LP, Xs, pf, tid);
+    if constexpr (WIN) {                                   // trial_x_first on the first window
+        if ((int)blockIdx.x < g.B) fz_win_prefetch<PF>(fold, C, T, blockIdx.x, pf, tid);
+        __syncthreads();
+        x_store<PF>(pf, C, T, RS, LP, Xs, tid);
+        __syncthreads();
+        drain_prologue_loads();
+    } else {
+        trial_x_first<PF>((int)blockIdx.x < g.B, xrow(blockIdx.x), C, T, RS, LP, Xs, pf, tid);
+    }
 
     for (int b = blockIdx.x; b < g.B; b += gridDim.x) {
         const int bnx = b + gridDim.x;
         const bool first = b == (int)blockIdx.x;
-        if (bnx < g.B) x_prefetch<PF>(xrow(bnx), C, T, pf, tid);
+        if constexpr (WIN) {
+            if (bnx < g.B) fz_win_prefetch<PF>(fold, C, T, bnx, pf, tid);
+        } else {
+            if (bnx < g.B) x_prefetch<PF>(xrow(bnx), C, T, pf, tid);
+        }
         // ---------------- forward ----------------
         spatial_mfma<KS>(Xs, w.aw, Ss, C, F2, NT16, RS, LP, wave, lane);
         __syncthreads();                                   // s rows complete
@@ -245,7 +294,9 @@ __global__ __launch_bounds__(NTH) void k_frozen(Geo g, const float* __restrict__
                 float l[NCLS];
 #pragma unroll
                 for (int n = 0; n < NCLS; ++n) l[n] = Lg[n];
-                const int cls = (int)lab[FOLD ? fold_row(perm, 0, b) : (long long)b];
+                int cls;
+                if constexpr (WIN) cls = (int)lab[fz_entry(fold, b)];      // the label follows the table entry
+                else cls = (int)lab[FOLD ? fold_row(perm, 0, b) : (long long)b];
                 float ex[NCLS], mx, lc = 0.f;
                 const float sum = softmax4(l, ex, mx);
 #pragma unroll

@@ -233,7 +233,12 @@ static void set_attrs_shape() {
                           (const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_CLS>,
                           (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_AGG>,
                           (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_B2>,
-                          (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_CLS>})
+                          (const void*)k_frozen<K1, CC, TT, FF, true, true, FZ_CLS>,
+                          // the windowed loader (eegnet_frozen_step_windows), every stage
+                          (const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_ALL, FzWin>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_AGG, FzWin>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_B2, FzWin>,
+                          (const void*)k_frozen<K1, CC, TT, FF, true, false, FZ_CLS, FzWin>})
         hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_eval_folds<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipFuncSetAttribute((const void*)k_infer_win<K1, CC, TT, FF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -771,20 +776,25 @@ static int frozen_geo(const eegnet_dims* dims, Geo* g) {
 static size_t frozen_ws_bytes(const Geo& g) { return rupz((size_t)g.grid * fz_cols(g).n * 4, 256); }
 
 // the backward instantiation of a shape for train_from (EEGNET_TRAIN_*, validated by frozen_offset)
-template <int K1, int CC, int TT, int FF, bool FOLD>
+// (Src: the loader policy, FzWin for the windows of a table)
+template <int K1, int CC, int TT, int FF, bool FOLD, class Src = FzFold<FOLD>>
 static auto frozen_bwd_kernel(int train_from) {
     switch (train_from) {
-        case EEGNET_TRAIN_FROM_AGGREGATION: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_AGG>;
-        case EEGNET_TRAIN_FROM_BLOCK2: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_B2>;
-        case EEGNET_TRAIN_FROM_CLASSIFIER: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_CLS>;
-        default: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_ALL>;
+        case EEGNET_TRAIN_FROM_AGGREGATION: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_AGG, Src>;
+        case EEGNET_TRAIN_FROM_BLOCK2: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_B2, Src>;
+        case EEGNET_TRAIN_FROM_CLASSIFIER: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_CLS, Src>;
+        default: return k_frozen<K1, CC, TT, FF, true, FOLD, FZ_ALL, Src>;
     }
 }
 
 static int frozen_launch(const char* name, const Geo& g, bool bwd, int train_from, const float* params,
                          const float* bn, const float* x, const float* dlogits, const int64_t* labels,
-                         const uint8_t* m2, const uint8_t* m3, float* logits, float* part, hipStream_t s) {
+                         const uint8_t* m2, const uint8_t* m3, float* logits, float* part, hipStream_t s,
+                         const FzWin* win = nullptr) {
     return dispatch_shape(g, [&](auto sh) {
+        if (win)                                      // x and the labels through the table (x is unused)
+            return launch(KID_NONE, name, frozen_bwd_kernel<SHAPE_OF(sh), false, FzWin>(train_from), dim3(g.grid),
+                          dim3(NTH), g.ldsX * 4, s, g, params, bn, x, dlogits, labels, m2, m3, logits, part, *win);
         return launch(KID_NONE, name,
                       bwd ? frozen_bwd_kernel<SHAPE_OF(sh), false>(train_from) : k_frozen<SHAPE_OF(sh), false>,
                       dim3(g.grid), dim3(NTH), g.ldsX * 4, s, g, params, bn, x, dlogits, labels, m2, m3, logits, part,
@@ -848,6 +858,29 @@ int eegnet_forward_frozen(const eegnet_dims* dims, const float* params, const fl
                          mask3, logits, nullptr, (hipStream_t)stream);
 }
 
+// eegnet_frozen_step_from behind its checks, for x as [B][C][T] or (win) the windows of a table: k_frozen, the
+// reduction of its partial rows and, with adam_state, Adam over the trainable suffix
+static int frozen_step_run(Geo& g, int off, int train_from, float* params, const float* bn_buffers, const float* x,
+                           const FzWin* win, const float* dlogits, const int64_t* labels, const uint8_t* mask2,
+                           const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads, float* adam_state,
+                           int32_t* step, float lr, float beta1, float beta2, float eps, float* loss, float* logits,
+                           void* ws, void* stream, int flags) {
+    if (int r = train_flags(&g, flags, seed, offset, step)) return r;
+    ensure_attrs();
+    hipStream_t s = (hipStream_t)stream;
+    float* part = (float*)ws;
+    if (int r = frozen_launch(win ? "k_frozen(windows)" : "k_frozen", g, true, train_from, params, bn_buffers, x, dlogits,
+                              labels, mask2, mask3, logits, part, s, win))
+        return r;
+    if (int r = launch(KID_NONE, "k_frozen_reduce", k_frozen_reduce<false>, dim3(frozen_reduce_grid(g, off)),
+                       dim3(NTFR), 0, s, g, params, bn_buffers, part, g.grid, grads, loss, off, FzFold<false>{})) return r;
+    if (!adam_state) return 0;
+    // the Adam kernel of eegnet_adam_step behind the reduction, over the trainable suffix; it advances the
+    // step counter last, after k_frozen has read it for the dropout key (EEGNET_KEY_FROM_STEP)
+    return eegnet_adam_step(g.nparam - off, params + off, grads + off, adam_state + off, adam_state + g.nparam + off,
+                            step, lr, beta1, beta2, eps, stream);
+}
+
 int eegnet_frozen_step_from(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,
                             const float* dlogits, const int64_t* labels, const uint8_t* mask2,
                             const uint8_t* mask3, uint64_t seed, uint64_t offset, float* grads,
@@ -865,20 +898,62 @@ int eegnet_frozen_step_from(const eegnet_dims* dims, float* params, const float*
     if (adam_state && !step) return fail(EEGNET_EINVAL, "step is NULL");
     if (int r = check_flags(flags, EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP, "frozen step: unknown flags 0x%x")) return r;
     if ((g.T & 3) == 0 && ((uintptr_t)x & 15)) return fail(EEGNET_EINVAL, "frozen BatchNorm: x must be 16-byte aligned");
-    if (int r = train_flags(&g, flags, seed, offset, step)) return r;
-    ensure_attrs();
-    hipStream_t s = (hipStream_t)stream;
-    float* part = (float*)ws;
-    if (int r = frozen_launch("k_frozen", g, true, train_from, params, bn_buffers, x, dlogits, labels, mask2, mask3,
-                              logits, part, s))
+    return frozen_step_run(g, off, train_from, params, bn_buffers, x, nullptr, dlogits, labels, mask2, mask3, seed, offset,
+                           grads, adam_state, step, lr, beta1, beta2, eps, loss, logits, ws, stream, flags);
+}
+
+// The frozen step on the windows a table places in continuous recordings (FzWin, eegnet_frozen.hip): the
+// checks of eegnet_frozen_step_from and of eegnet_forward_eval_windows_at, none of which needs a GPU.
+int eegnet_frozen_step_windows(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* rec,
+                               int64_t n_rec, int64_t n_samples, int64_t pitch, const int64_t* starts,
+                               const int32_t* rec_index, const int64_t* labels, int64_t n_table, const int64_t* sel,
+                               const float* dlogits, const uint8_t* mask2, const uint8_t* mask3, uint64_t seed,
+                               uint64_t offset, float* grads, float* adam_state, int32_t* step, float lr, float beta1,
+                               float beta2, float eps, float* loss, float* logits, void* ws, void* stream, int flags,
+                               int train_from) {
+    Geo g;
+    if (int r = frozen_geo(dims, &g)) return r;
+    int off;
+    if (int r = frozen_offset(g, train_from, &off)) return r;
+    if (int r = check_ptrs(params, "params", bn_buffers, "bn_buffers")) return r;
+    if (int r = check_ptrs(rec, "rec", grads, "grads")) return r;
+    if (int r = check_ptrs(starts, "starts", ws, "ws")) return r;
+    if (!dlogits && !labels) return fail(EEGNET_EINVAL, "frozen step on windows: need dlogits or labels");
+    if (dlogits && labels) return fail(EEGNET_EINVAL, "frozen step on windows: dlogits and labels are exclusive");
+    if (adam_state && !step) return fail(EEGNET_EINVAL, "step is NULL");
+    if (int r = check_flags(flags, EEGNET_NO_CLAMP | EEGNET_KEY_FROM_STEP, "frozen step on windows: unknown flags 0x%x"))
         return r;
-    if (int r = launch(KID_NONE, "k_frozen_reduce", k_frozen_reduce<false>, dim3(frozen_reduce_grid(g, off)),
-                       dim3(NTFR), 0, s, g, params, bn_buffers, part, g.grid, grads, loss, off, FzFold<false>{})) return r;
-    if (!adam_state) return 0;
-    // the Adam kernel of eegnet_adam_step behind the reduction, over the trainable suffix; it advances the
-    // step counter last, after k_frozen has read it for the dropout key (EEGNET_KEY_FROM_STEP)
-    return eegnet_adam_step(g.nparam - off, params + off, grads + off, adam_state + off, adam_state + g.nparam + off,
-                            step, lr, beta1, beta2, eps, stream);
+    if (n_rec < 1 || n_rec > 2147483647)
+        return fail(EEGNET_EINVAL, "frozen step on windows: n_rec must be in [1, 2^31) (got %lld)", (long long)n_rec);
+    if (n_samples < g.T)
+        return fail(EEGNET_EINVAL, "frozen step on windows: n_samples = %lld is shorter than one window (T = %d)",
+                    (long long)n_samples, g.T);
+    if (pitch < n_samples)
+        return fail(EEGNET_EINVAL, "frozen step on windows: pitch = %lld is below n_samples = %lld", (long long)pitch,
+                    (long long)n_samples);
+    if (((uintptr_t)rec & 3) || ((uintptr_t)starts & 7) || ((uintptr_t)rec_index & 3) || ((uintptr_t)labels & 7) ||
+        ((uintptr_t)sel & 7))
+        return fail(EEGNET_EINVAL, "frozen step on windows: rec, starts, rec_index, labels and sel must be aligned to "
+                    "their element size");
+    if (n_table < 1 || n_table > 2147483647)
+        return fail(EEGNET_EINVAL, "frozen step on windows: n_table must be in [1, 2^31) (got %lld)", (long long)n_table);
+    if (!sel && g.B > n_table)
+        return fail(EEGNET_EINVAL, "frozen step on windows: B = %d windows exceed the table's %lld entries (no sel)", g.B,
+                    (long long)n_table);
+    FzWin fw;
+    fw.ac.rec = rec;
+    fw.ac.pitch = pitch;
+    fw.ac.hop = 0;
+    fw.ac.W = 0;
+    fw.ac.total = (int)n_table;
+    fw.ac.vec = 0;
+    fw.ac.starts = (const long long*)starts;
+    fw.ac.rec_index = rec_index;
+    fw.ac.last = n_samples - g.T;
+    fw.ac.n_rec = (int)n_rec;
+    fw.sel = (const long long*)sel;
+    return frozen_step_run(g, off, train_from, params, bn_buffers, nullptr, &fw, dlogits, labels, mask2, mask3, seed,
+                           offset, grads, adam_state, step, lr, beta1, beta2, eps, loss, logits, ws, stream, flags);
 }
 
 int eegnet_frozen_step(const eegnet_dims* dims, float* params, const float* bn_buffers, const float* x,

@@ -40,9 +40,9 @@
 #include "eegnet_trial.hip"
 #include "eegnet_passes.hip"
 #include "eegnet_input_grad.hip"
+#include "eegnet_windows.hip"     // (before eegnet_frozen.hip: k_frozen's windowed loader is its WinAtCall)
 #include "eegnet_frozen.hip"
 #include "eegnet_eval_folds.hip"
-#include "eegnet_windows.hip"
 #include "eegnet_wide.hip"
 #include "eegnet_infer_bf16.hip"
 #include "eegnet_infer_bf16c.hip"

@@ -540,18 +540,7 @@ def epoch_starts(onsets, sfreq=128.0, tmin=0.5):
     return onsets.to(torch.int64) + int(round(float(tmin) * float(sfreq)))
 
 
-def _host_table(t, what, dtype, lo, hi, why):
-    """A host table (list, numpy array, CPU tensor) as a CPU tensor of ``dtype``, every entry in [lo, hi]."""
-    t = torch.as_tensor(t)
-    if t.numel() == 0 and t.dim() == 1:
-        t = t.to(torch.int64)                                   # (an empty list comes as float32)
-    if t.is_floating_point() or t.dtype == torch.bool or t.dim() != 1:
-        raise ValueError(f"{what} must be a 1-D table of integers (got {t.dtype} {list(t.shape)})")
-    t = t.to(torch.int64)
-    if t.numel() and (int(t.min()) < lo or int(t.max()) > hi):
-        bad = int(((t < lo) | (t > hi)).nonzero()[0])
-        raise ValueError(f"{what}[{bad}] = {int(t[bad])} is outside [{lo}, {hi}] ({why})")
-    return t.to(dtype).contiguous()
+_host_table = ops.host_table
 
 
 def epoch_logits(model, rec, starts, rec_index=None):
@@ -748,6 +737,94 @@ class FusedTrainer:
                        self.loss, logits=logits, lr=self.lr, betas=self.betas, eps=self.eps,
                        nbt=nbt)
         return self.loss
+
+    def step_epochs(self, rec, starts, y, rec_index=None, sel=None, logits=None):
+        """The frozen-BatchNorm branch of ``step`` on windows of continuous recordings read in place
+        (``ops.frozen_step_windows``): batch row b is table entry ``sel[b]`` (b when ``sel`` is None), samples
+        [starts[e], starts[e] + T) of recording ``rec_index[e]`` of ``rec`` with label ``y[e]``.  The dropout
+        key sequence (``next_dropout_key``), the injected masks, the ``train_from`` stage and the Adam state
+        are ``step``'s, so the parameters, the moments, the step counter and the loss come out bit-identical
+        to ``step`` on the windows copied out.  Device tables are clamped by the kernel, host tables checked
+        (``ops.frozen_step_windows``).  RuntimeError unless the model is ``freeze_bn()``-ed: the five-pass
+        train step reads contiguous trials."""
+        m = self.model
+        if not getattr(m, "bn_frozen", False):
+            raise RuntimeError("step_epochs is the frozen-BatchNorm step on windows: call model.freeze_bn() first "
+                               "(the train-mode step with batch statistics takes contiguous trials, FusedTrainer.step)")
+        seed, offset = m.next_dropout_key()
+        flat, bn_flat, _ = m.flat_views()
+        B = len(sel) if sel is not None else len(starts)
+        masks = m._masks
+        if masks is not None and masks[0].shape[0] != B:
+            raise RuntimeError("injected dropout masks do not match the batch size")
+        stage = m._stage_checked()
+        try:
+            ops.frozen_step_windows(m.shape, flat, bn_flat, rec, starts, y, seed, offset, self.adam.grads,
+                                    self.frozen_workspace(B), rec_index=rec_index, sel=sel, masks=masks,
+                                    adam_state=self.adam.state, step_i32=self.adam.step, loss=self.loss,
+                                    logits=logits, lr=self.lr, betas=self.betas, eps=self.eps, train_from=stage)
+        except RuntimeError as e:
+            _not_supported(e)
+        return self.loss
+
+
+def batch_slices(n, batch_size):
+    """The (begin, end) slices of a permutation of n entries a loop at ``batch_size`` takes: ceil(n / batch_size)
+    of them, the last one short (``DataLoader(shuffle=True)`` without ``drop_last``)."""
+    n, batch_size = int(n), int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1 (got {batch_size})")
+    return [(i, min(i + batch_size, n)) for i in range(0, n, batch_size)]
+
+
+def finetune_on_recording(model, rec, starts, labels, rec_index=None, *, epochs=1, batch_size=64, lr=1e-3,
+                          betas=(0.9, 0.999), eps=1e-7, optimizer=None, generator=None, trainer=None):
+    """Fine-tune a ``freeze_bn()``-ed model on the cue epochs of continuous recordings as they lie in memory:
+    epoch e of the table is samples [starts[e], starts[e] + T) of recording ``rec_index[e]`` of ``rec``
+    [R, C, N] (recording 0 when ``rec_index`` is None, and for [C, N]) with label ``labels[e]``
+    (``epoch_starts`` gives the reference's starts from the cue onsets).  No epoch is copied out and no batch
+    gathered: per epoch one ``torch.randperm(n, device=..., generator=...)`` is drawn and ceil(n / batch_size)
+    ``FusedTrainer.step_epochs`` calls run, each on ``sel = perm[i : i + batch_size]``, the last one short.
+    Host tables are checked once (ValueError for a start outside [0, N - T], a recording outside [0, R) or a
+    label outside the classes) and uploaded; device tables are used as they lie, clamped by the kernel.  What
+    trains is what ``EEGNet.train_from`` left trainable.
+
+    Every step is bit-identical to ``FusedTrainer.step`` on the batch's windows gathered into a contiguous
+    [B, C, T] tensor.  Returns ``(losses, trainer)``: the per-step mean cross-entropies as a device tensor
+    [epochs, steps], written on the stream without a host read, and the trainer (``trainer`` when given, else a
+    new one over ``lr`` / ``betas`` / ``eps`` -- or the single parameter group of ``optimizer``, a
+    ``torch.optim.Adam`` whose state is loaded first and stored back at the end, as ``train`` does)."""
+    if not getattr(model, "bn_frozen", False):
+        raise RuntimeError("finetune_on_recording fine-tunes with frozen BatchNorm: call model.freeze_bn() first")
+    require_device(rec, "EEGNet recording")
+    if rec.dim() not in (2, 3) or rec.shape[-2] != model.C or rec.shape[-1] < model.T:
+        raise RuntimeError(f"expected a recording [{model.C}, N] or [R, {model.C}, N] with N >= {model.T}, "
+                           f"got {list(rec.shape)}")
+    dev = rec.device
+    R, N = (1 if rec.dim() == 2 else int(rec.shape[0])), int(rec.shape[-1])
+    # host tables are checked and uploaded once, here; step_epochs then sees device tables
+    if not (isinstance(starts, torch.Tensor) and starts.device.type == "cuda"):
+        starts = _host_table(starts, "starts", torch.int64, 0, N - model.T,
+                             f"a window of T = {model.T} samples in a recording of {N}").to(dev)
+    if rec_index is not None and not (isinstance(rec_index, torch.Tensor) and rec_index.device.type == "cuda"):
+        rec_index = _host_table(rec_index, "rec_index", torch.int32, 0, R - 1, f"{R} recordings").to(dev)
+    if not (isinstance(labels, torch.Tensor) and labels.device.type == "cuda"):
+        labels = _host_table(labels, "labels", torch.int64, 0, ops.NCLS - 1, f"{ops.NCLS} classes").to(dev)
+    n = int(starts.shape[0])
+    if trainer is None:
+        if optimizer is not None:
+            grp = optimizer.param_groups[0]
+            lr, betas, eps = grp["lr"], grp["betas"], grp["eps"]
+        trainer = FusedTrainer(model, lr=lr, betas=betas, eps=eps, optimizer=optimizer)
+    slices = batch_slices(n, batch_size)
+    losses = torch.zeros((int(epochs), len(slices)), dtype=torch.float32, device=dev)
+    for e in range(int(epochs)):
+        perm = torch.randperm(n, device=dev, generator=generator)
+        for k, (i, j) in enumerate(slices):
+            losses[e, k:k + 1].copy_(trainer.step_epochs(rec, starts, labels, rec_index, sel=perm[i:j]))
+    if optimizer is not None:
+        trainer.adam.store_to(model, optimizer)
+    return losses, trainer
 
 
 def train(model, optimizer, loss_fn, train_loader, val_loader, nepochs=500, *, true_best=False,

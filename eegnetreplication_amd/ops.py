@@ -592,6 +592,88 @@ def frozen_step(shape: Shape, flat_params, bn_flat, x, seed: int, offset: int, g
     return grads
 
 
+def host_table(t, what, dtype, lo, hi, why):
+    """A host table (list, numpy array, CPU tensor) as a CPU tensor of ``dtype``, every entry in [lo, hi]."""
+    t = torch.as_tensor(t)
+    if t.numel() == 0 and t.dim() == 1:
+        t = t.to(torch.int64)                                   # (an empty list comes as float32)
+    if t.is_floating_point() or t.dtype == torch.bool or t.dim() != 1:
+        raise ValueError(f"{what} must be a 1-D table of integers (got {t.dtype} {list(t.shape)})")
+    t = t.to(torch.int64)
+    if t.numel() and (int(t.min()) < lo or int(t.max()) > hi):
+        bad = int(((t < lo) | (t > hi)).nonzero()[0])
+        raise ValueError(f"{what}[{bad}] = {int(t[bad])} is outside [{lo}, {hi}] ({why})")
+    return t.to(dtype).contiguous()
+
+
+def _table(t, what, dtype, device, lo, hi, why):
+    """A table of ``frozen_step_windows``: a device tensor (contiguous, of ``dtype``, on ``device``) as it
+    lies and unread; a host table checked by ``host_table`` and uploaded."""
+    if isinstance(t, torch.Tensor) and t.device.type == "cuda":
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{what} must be a contiguous {dtype} 1-D tensor on {device}")
+        return t
+    return host_table(t, what, dtype, lo, hi, why).to(device)
+
+
+def frozen_step_windows(shape: Shape, flat_params, bn_flat, rec, starts, labels, seed: int, offset: int, grads, ws,
+                        *, rec_index=None, sel=None, dlogits=None, masks=None, adam_state=None, step_i32=None,
+                        loss=None, logits=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-7, p: float | None = None,
+                        clamp=True, key_from_step=False, train_from=0):
+    """``frozen_step`` on windows of continuous recordings read in place (eegnet_frozen_step_windows): batch
+    row b is table entry e = ``sel[b]`` (b when ``sel`` is None), its x samples [starts[e], starts[e] + T) of
+    recording ``rec_index[e]`` (None: recording 0) and its label ``labels[e]``; ``dlogits`` [B, 4] (instead
+    of ``labels``), ``logits`` [B, 4] and the ``masks`` are indexed by the batch row.  B = len(sel), else
+    len(starts); ``ws`` from ``new_frozen_workspace`` for B.
+
+    ``rec`` [C, N] or [R, C, N] float32 is read where it lies when its last stride is 1 and the recording
+    stride is C times the channel stride (a contiguous tensor or a time slice of one, at any 4-byte
+    alignment), else through one contiguous copy; it is never written.  A device table (``starts`` /
+    ``labels`` / ``sel`` int64, ``rec_index`` int32) is used as it lies and never read by the host, and the
+    kernel clamps its entries: a start into [0, N - T], a recording into [0, R), a ``sel`` entry into the
+    table.  A host table (list, numpy array, CPU tensor) is checked against those ranges (ValueError) and
+    uploaded.
+
+    ``grads`` on the trainable suffix, ``loss``, ``logits``, the parameters and both Adam moments after the
+    update and the step counter are bit-identical to ``frozen_step`` on the batch's windows copied out into a
+    contiguous [B, C, T] with the labels gathered, for the same (seed, offset) or masks, flags and
+    ``train_from``."""
+    require_device(rec, "rec")
+    if rec.dtype != torch.float32:
+        raise RuntimeError(f"frozen_step_windows expects a float32 recording (got {rec.dtype})")
+    if rec.dim() not in (2, 3) or rec.shape[-2] != shape.C:
+        raise RuntimeError(f"expected a recording [{shape.C}, N] or [R, {shape.C}, N], got {list(rec.shape)}")
+    r3 = rec.unsqueeze(0) if rec.dim() == 2 else rec
+    R, C, N = r3.shape
+    pitch = _row_pitch(r3)
+    if pitch is None:
+        r3, pitch = r3.contiguous(), N
+    dev = rec.device
+    starts = _table(starts, "starts", torch.int64, dev, 0, N - shape.T,
+                    f"a window of T = {shape.T} samples in a recording of {N}")
+    n = int(starts.shape[0])
+    if rec_index is not None:
+        rec_index = _table(rec_index, "rec_index", torch.int32, dev, 0, R - 1, f"{R} recordings")
+    if labels is not None:
+        labels = _table(labels, "labels", torch.int64, dev, 0, NCLS - 1, f"{NCLS} classes")
+    for name, t in (("rec_index", rec_index), ("labels", labels)):
+        if t is not None and int(t.shape[0]) != n:
+            raise ValueError(f"{name} holds {int(t.shape[0])} entries, starts {n}")
+    if sel is not None:
+        sel = _table(sel, "sel", torch.int64, dev, 0, n - 1, f"a table of {n} entries")
+    B = n if sel is None else int(sel.shape[0])
+    m2, m3 = masks if masks is not None else (None, None)
+    _lib.check(_lib.load().eegnet_frozen_step_windows(
+        ctypes.byref(shape.dims(B, p)), _ptr(flat_params), _ptr(bn_flat), _ptr(r3), ctypes.c_int64(R),
+        ctypes.c_int64(N), ctypes.c_int64(pitch), _ptr(starts), _ptr(rec_index), _ptr(labels), ctypes.c_int64(n),
+        _ptr(sel), _ptr(dlogits), _ptr(m2), _ptr(m3), ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(grads),
+        _ptr(adam_state), _ptr(step_i32), ctypes.c_float(lr), ctypes.c_float(betas[0]), ctypes.c_float(betas[1]),
+        ctypes.c_float(eps), _ptr(loss), _ptr(logits), _ptr(ws), _stream(),
+        (0 if clamp else NO_CLAMP) | (KEY_FROM_STEP if key_from_step else 0), ctypes.c_int(stage_index(train_from))),
+        "eegnet_frozen_step_windows")
+    return grads
+
+
 def forward_eval_bf16(shape: Shape, flat_params, bn_flat, x) -> torch.Tensor:
     """Eval-mode forward on bf16 input (bf16 MFMA operands, fp32 accumulation, fp32 logits)."""
     if x.dtype != torch.bfloat16:

@@ -377,6 +377,31 @@ int eegnet_forward_eval_windows_at(const eegnet_dims* dims, const float* params,
                                    const int64_t* starts, const int32_t* rec_index, int64_t n_windows,
                                    float* logits, void* stream);
 
+/* Fine-tuning on cue epochs read in place: eegnet_frozen_step_from on windows of continuous recordings that
+ * a table places, without copying them out.  `rec`, n_rec, n_samples, pitch, starts and rec_index are
+ * eegnet_forward_eval_windows_at's, the table having n_table entries; dims->B is the batch, the windows of
+ * this step.  Batch row b is table entry e = sel ? clamp(sel[b], 0, n_table - 1) : b (sel: int64 [B], DEVICE,
+ * nullable; B <= n_table without it): its x is samples [starts[e], starts[e] + T) of recording rec_index[e],
+ * both clamped into the recordings as in eegnet_forward_eval_windows_at, and its mean-CE label is labels[e]
+ * (labels: int64 [n_table]).  dlogits [B, 4], logits [B, 4], mask2 / mask3 and the dropout counters are
+ * indexed by the batch row b.  Exactly one of labels and dlogits is given; every other argument, the flags,
+ * train_from and ws (eegnet_frozen_workspace_bytes(dims)) are eegnet_frozen_step_from's.
+ * Every output -- grads on the trainable suffix, loss, logits, params and both Adam moments after the update,
+ * the step counter -- is bit-identical to eegnet_frozen_step_from on the batch's windows copied out into a
+ * contiguous [B, C, T] x with the labels gathered, for the same (seed, offset) or masks, flags and train_from.
+ * rec needs 4-byte alignment only (the load width is chosen per window on the device) and is never written;
+ * the host never reads a table.  n_rec and n_table in [1, 2^31), n_samples >= T, pitch >= n_samples, tables
+ * aligned to their element size, x_pitch 0 or T, F1*D <= 16 only.  No atomics, no allocation, no host
+ * synchronisation: capturable in a hipGraph.  The validation needs no GPU. */
+int eegnet_frozen_step_windows(const eegnet_dims* dims, float* params, const float* bn_buffers,
+                               const float* rec, int64_t n_rec, int64_t n_samples, int64_t pitch,
+                               const int64_t* starts, const int32_t* rec_index, const int64_t* labels,
+                               int64_t n_table, const int64_t* sel,
+                               const float* dlogits, const uint8_t* mask2, const uint8_t* mask3, uint64_t seed,
+                               uint64_t offset, float* grads, float* adam_state, int32_t* step, float lr,
+                               float beta1, float beta2, float eps, float* loss, float* logits, void* ws,
+                               void* stream, int flags, int train_from);
+
 /* FIR filtering of continuous recordings: the reference's zero-phase band-pass (raw.filter(4., 38.,
  * fir_design='firwin'), dataset.py:113-125; a 213-tap FIR at 128 Hz) for any taps, the step in front of
  * eegnet_ems.  Per row, with taps h[0..L-1] (fp64, on the device; L = n_taps) and M = (L-1)/2,
